@@ -28,6 +28,12 @@ object per further workload under "also".  The headline's `value`, `ms_per_step`
 of rays on the GPU at a time (BASELINE's "1 M parallel rays"); what several batches in
 flight on streams of their own reach is measured in a second region and reported
 beside it (`in_flight`).
+
+--dump-outputs DIR: after the timed region, what its LAST pass handed its caller (the headline
+workload's arrays: a trace's end positions, media, path lengths and step counts; a walk's state)
+and the tally, as DIR/<name>.npy in float64, at most 64 MB in all -- past that, a fixed, seeded
+sample of the rays, whose numbers are in DIR/ray.npy.  The inputs depend on the arguments alone,
+so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -55,6 +61,8 @@ WALK_N_KERNELS = "k_step_fast + k_bisect per generation (turtle_stepper_walk_n: 
 WALK_KERNEL = "k_walk (a ray's whole walk in one launch: state in registers, directions drawn in the kernel)"
 SEED = 0x5EED2026
 PARITY_RAYS = 100_000
+DUMP_BYTES = 64_000_000     # --dump-outputs: all files together
+DUMP_SEED = 0xD0A9
 
 WORKLOADS = {
     # name: (tiles (lat0, lon0, nlat, nlon), through a stack?, default rays/GPU, text)
@@ -229,6 +237,35 @@ def parity_counts(index, length, ref_index, ref_length, steps=None, ref_steps=No
     return out
 
 
+def dump_outputs(directory, per_ray, whole):
+    """--dump-outputs: `per_ray` (tensors with one row a ray) and `whole` (tensors kept entire)
+    as DIR/<name>.npy in float64 (integers too: exact below 2**53).  Past DUMP_BYTES in all, the
+    same fixed, seeded sample of rows from every per-ray array, in ray order, their numbers in
+    ray.npy.  Returns what was written, for the workload's record."""
+    import torch
+    per_ray = {k: v for k, v in per_ray.items() if v is not None}
+    n = next(iter(per_ray.values())).shape[0]
+    row = sum(8 * int(np.prod(v.shape[1:])) for v in per_ray.values())
+    fixed = sum(8 * v.numel() for v in whole.values())
+    arrays, rows = dict(whole), None
+    if fixed + n * row > DUMP_BYTES:
+        k = (DUMP_BYTES - fixed) // (row + 8)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+        pick = torch.as_tensor(rows, device=next(iter(per_ray.values())).device)
+        per_ray = {name: v.index_select(0, pick) for name, v in per_ray.items()}
+        arrays["ray"] = rows
+    arrays.update(per_ray)
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, v in arrays.items():
+        a = v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        total += a.nbytes
+    return {"dir": directory, "files": sorted(arrays), "rays": n if rows is None else int(rows.size),
+            "of_rays": n, "bytes": total}
+
+
 def cpu_baseline(terrain, pos, d, cores):
     """The reference itself (oracle/_ref, kind "reference") where its build
     travelled with the repo and the terrain is a single map, else the CPU
@@ -386,6 +423,7 @@ def run_workload(name, args, env, headline):
                 taken += alive.to(torch.int32)
         if count:
             return {"index": st["index"].clone(), "length": total, "steps": taken}
+        f.last = st                  # what the caller of the last generation received
         f.gen_ev[1].record()
         f.gen_ms.append(f.gen_ev)
         return None
@@ -470,6 +508,13 @@ def run_workload(name, args, env, headline):
     # THE timed region: one batch on the GPU at a time.  value, ms_per_step, kernel.ms and
     # the roofline are all this region's.
     elapsed, kernel_ms = region(steps, flights[:1])
+    dumped = None
+    if headline and args.dump_outputs and rank == 0:
+        # (before the region in flight below, whose passes write the same arrays again)
+        f = flights[0]
+        got = ({"position": f.pos, "index": f.index, "length": f.length, "n_steps": f.nsteps}
+               if not scatter else dict(f.last if gens else f.walk))
+        dumped = dump_outputs(args.dump_outputs, got, {"tally": tally})
     stats = stepper.trace_stats()            # of the last pass on this rank
     if gens:
         # step_n keeps no totals: the replica's count, and SURVEY's 1.05 samples a step
@@ -551,6 +596,8 @@ def run_workload(name, args, env, headline):
             "tally": {"hits": [int(v) for v in tally[t_hits].tolist()],
                       "sha256": hashlib.sha256(tally.cpu().numpy().tobytes()).hexdigest()[:16]},
         }
+        if dumped is not None:
+            out["outputs"] = dumped
         # ---- parity of what was just timed, and the CPU beside it ----
         if not args.no_cpu and world == 1:
             cores = host_cores()
@@ -779,7 +826,12 @@ def main():
     ap.add_argument("--generations", type=int, default=64, help="generations of the default c5!step_n leg")
     ap.add_argument("--tiles", choices=("auto", "hgt", "tif"), default="auto",
                     help="tile files: SRTM's .hgt, ASTER-GDEM2's GeoTIFF-16 (auto: tif for c5, hgt else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(float64; beyond 64 MB in all, a fixed, seeded sample of the rays)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `bench.py --gpus N` on its own: start the N ranks as a CHILD job (before anything here
     # has touched a GPU: a process that has must never exec), relay rank 0's line and code

@@ -2,8 +2,9 @@
 
 Exists only in the build container, where oracle/Makefile compiles the
 reference from /root/reference in place.  Used by tests/golden/generate.py to
-produce the committed fixtures and by tests/test_oracle_vs_reference.py (which
-skips when the library is absent, e.g. on the GPU box).  TEST INFRASTRUCTURE.
+produce the committed fixtures that pin the restatement (tests/test_oracle_golden.py,
+tests/test_oracle_vs_reference.py) and by bench.py's CPU baseline where the build
+is present.  TEST INFRASTRUCTURE.
 """
 from __future__ import annotations
 

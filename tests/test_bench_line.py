@@ -64,3 +64,33 @@ def test_last_line_is_short_and_carries_the_headline():
     text = json.dumps(bench.final_line(_record("c2", 4000), many, args, 8, "nccl", 8))
     assert len(text) < bench.LINE_LIMIT, len(text)
     assert json.loads(text)["comm_world_size"] == 8 and json.loads(text)["backend"] == "nccl"
+
+
+def test_dump_outputs_whole_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array as float64 .npy; past the byte budget the same seeded rows of
+    every per-ray array (their numbers in ray.npy), the same from run to run, within the budget"""
+    import numpy as np
+    import torch
+    import bench
+    n = 5000
+    got = {"position": torch.arange(3 * n, dtype=torch.float64).reshape(n, 3),
+           "index": torch.arange(2 * n, dtype=torch.int32).reshape(n, 2),
+           "length": torch.arange(n, dtype=torch.float64) * 0.5,
+           "n_steps": torch.arange(n, dtype=torch.int32), "latitude": None}
+    tally = torch.arange(7, dtype=torch.int64)
+    whole = bench.dump_outputs(str(tmp_path / "whole"), got, {"tally": tally})
+    assert whole["rays"] == n and "ray" not in whole["files"]
+    for name in ("position", "index", "length", "n_steps", "tally"):
+        a = np.load(tmp_path / "whole" / (name + ".npy"))
+        assert a.dtype == np.float64
+        assert np.array_equal(a, (got[name] if name != "tally" else tally).numpy())
+    assert not (tmp_path / "whole" / "latitude.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100_000)
+    runs = [bench.dump_outputs(str(tmp_path / f"sample{k}"), got, {"tally": tally}) for k in range(2)]
+    assert runs[0]["rays"] == runs[1]["rays"] < n and runs[0]["bytes"] <= 100_000
+    rows = np.load(tmp_path / "sample0" / "ray.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "sample1" / "ray.npy")) and (np.diff(rows) > 0).all()
+    for name in ("position", "index", "length", "n_steps"):
+        a = np.load(tmp_path / "sample0" / (name + ".npy"))
+        assert np.array_equal(a, got[name].numpy()[rows])
+    assert sum(f.stat().st_size for f in (tmp_path / "sample0").iterdir()) < 100_000 + 1024

@@ -1077,6 +1077,47 @@ def test_two_ranks_share_the_gpu_through_bench(tmp_path):
     assert bad.returncode != 0
 
 
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
+    """bench.py --dump-outputs: --steps passes timed, and the arrays of the last one written as
+    float64 .npy -- the tally in the result line is theirs, and they agree with the CPU oracle"""
+    import hashlib
+    import json
+    import subprocess
+    import sys
+    from turtle_amd import sharding
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    n = 60000
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "c2",
+                          "--rays", str(n), "--steps", "3", "--warmup", "1", "--no-cpu", "--also", "none",
+                          "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=root)
+    rows = [l for l in run.stdout.splitlines() if l.startswith("{")]
+    assert run.returncode == 0 and len(rows) == 2, (run.stdout[-500:], run.stderr[-1500:])
+    line, record = json.loads(rows[-1]), json.loads(rows[0])
+    assert line["steps"] == 3 and record["steps"] == 3 and line["ms_per_step"] > 0
+    assert record["outputs"]["rays"] == n and "ray" not in record["outputs"]["files"]
+    got = {name: np.load(out / (name + ".npy")) for name in ("position", "index", "length", "n_steps", "tally")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["position"].shape == (n, 3) and got["index"].shape == (n, 2) and got["length"].shape == (n,)
+    tally = got["tally"].astype(np.int64)
+    assert hashlib.sha256(tally.tobytes()).hexdigest()[:16] == line["tally"]["sha256"]
+    hits, _, steps, _ = sharding.tally_layout(2, 1024)
+    assert tally[steps] == got["n_steps"].sum() and tally[hits].sum() == n
+    # bench.py's C2 rays set up as it does, their first ones traced by the oracle
+    m = 2000
+    lat, lon, az, el = (v[:m] for v in sharding.rank_rays(n, 0, (45.0, 46.0), (3.0, 4.0)))
+    tile = B.hgt_tile(tmp_path)
+    st = B.c1_stepper(tile)
+    pos, _ = st.position(lat, lon, 500.0)
+    d = TA.ecef_from_horizontal(lat, lon, az, el)
+    st.destroy()
+    tile.destroy()
+    _, geo = T.hgt_oracle(45, 3)
+    ref = geo.trace(pos, d, local_range=0.0, threads=8)
+    assert np.array_equal(got["index"][:m], ref["index"])
+    assert (np.abs(got["length"][:m] - ref["length"]) <= 1e-6 * np.abs(ref["length"])).all()
+
+
 @pytest.mark.parametrize("fmt", ["hgt", "tif"])
 def test_scatter_over_a_stack_against_the_oracle(math, tmp_path, fmt):
     """Config C5 in small, on its real kind of terrain: a walk of 64 generations over a

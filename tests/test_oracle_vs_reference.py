@@ -1,49 +1,59 @@
-"""The CPU restatement (oracle/) against the REAL reference, live: where the
-reference's build is present (oracle/_ref/, made by oracle/Makefile in the build
-container; it also travels to the GPU box) the same rays are stepped by both and
-must agree bit for bit -- medium, data index, step count, path length -- with the
-exact transform (range 0) and with the reference's local approximation (range 1).
-Skipped where the build is absent; the committed golden vectors (test_oracle_golden)
-pin the restatement there."""
+"""The CPU restatement (oracle/) against the REAL reference on whole batches: the reference's
+outputs for the same rays are stored in tests/golden/vs_reference.npz (written by
+tests/golden/generate_vs_reference.py, which drives the reference's build under oracle/_ref/),
+and the restatement must agree with them bit for bit -- medium, data index, step count, path
+length, end position -- with the exact transform (range 0) and with the reference's local
+approximation (range 1)."""
 import numpy as np
 import pytest
 
 from oracle import ffi as O
-from oracle import ref_ffi as R
 from turtle_amd import synth
 
 import terrains as T
 
-pytestmark = pytest.mark.skipif(not R.driver_available(),
-                                reason="oracle/_ref (the compiled reference) is not present")
+N_NODES, N_RAYS, WALK_STEPS = 1201, 6000, 48
+WALK_TILES = [(45, 0), (45, 1)]
+
+
+def test_stored_inputs_are_the_recipe(golden):
+    """the terrain and the rays the reference stepped are still what the recipes make"""
+    g = golden("vs_reference")
+    assert T.sha(synth.srtm_like_nodes(45, 3, N_NODES)) == str(g["trace_nodes_sha"])
+    assert [T.sha(synth.srtm_like_nodes(la, lo, N_NODES)) for la, lo in WALK_TILES] == \
+        [str(s) for s in g["walk_nodes_sha"]]
+    _, geo = T.hgt_oracle(45, 3, N_NODES)
+    lat, lon, az, el = synth.uniform_rays(N_RAYS, (45.0, 46.0), (3.0, 4.0), seed=21)
+    pos, _ = geo.position(lat, lon, 500.0)
+    assert np.array_equal(pos, g["trace_position"])
+    assert np.array_equal(O.ecef_from_horizontal(lat, lon, az, el), g["trace_direction"])
+    geo = T.mosaic_oracle(WALK_TILES, N_NODES, 45, 0, 1, 2)
+    lat, lon, _, _ = synth.uniform_rays(N_RAYS, (45.0, 46.0), (0.0, 2.0), seed=5)
+    pos, _ = geo.position(lat, lon, np.full(N_RAYS, 20000.0))
+    assert np.array_equal(pos, g["walk_position"])
 
 
 @pytest.mark.parametrize("local_range", [0.0, 1.0])
-def test_traces_equal_bit_for_bit(tmp_path, local_range):
-    n_nodes = 1201
-    path = synth.write_hgt(str(tmp_path), 45, 3, n_nodes)
-    _, geo = T.hgt_oracle(45, 3, n_nodes)
-    lat, lon, az, el = synth.uniform_rays(6000, (45.0, 46.0), (3.0, 4.0), seed=21)
-    pos, _ = geo.position(lat, lon, 500.0)
-    d = O.ecef_from_horizontal(lat, lon, az, el)
-    theirs = R.trace_map(path, pos, d, local_range=local_range, threads=4)
+def test_traces_equal_bit_for_bit(golden, local_range):
+    g = golden("vs_reference")
+    r = f"trace{int(local_range)}_"
+    _, geo = T.hgt_oracle(45, 3, N_NODES)
+    pos, d = g["trace_position"], g["trace_direction"]
     ours = geo.trace(pos, d, local_range=local_range, threads=4)
-    assert theirs["total_steps"] == ours["total_steps"] > 500_000
-    assert np.array_equal(theirs["index"], ours["index"])
-    assert np.array_equal(theirs["n_steps"], ours["n_steps"])
-    assert np.array_equal(theirs["length"], ours["length"])          # bit for bit
-    assert np.array_equal(theirs["position"], ours["position"])
+    assert int(g[r + "total_steps"]) == ours["total_steps"] > 500_000
+    assert np.array_equal(g[r + "index"], ours["index"])
+    assert np.array_equal(g[r + "n_steps"], ours["n_steps"])
+    assert np.array_equal(g[r + "length"], ours["length"])          # bit for bit
+    assert np.array_equal(g[r + "end"], ours["position"])
     # the cap and a ray that starts outside
-    theirs = R.trace_map(path, pos[:64], d[:64], local_range=local_range, max_steps=9)
     ours = geo.trace(pos[:64], d[:64], local_range=local_range, max_steps=9)
-    assert np.array_equal(theirs["n_steps"], ours["n_steps"]) and (ours["n_steps"] <= 9).all()
-    far = pos[:4] * 3.0
-    theirs, ours = R.trace_map(path, far, d[:4]), geo.trace(far, d[:4], local_range=1.0)
-    assert (theirs["index"][:, 0] == -1).all() and np.array_equal(theirs["index"], ours["index"])
+    assert np.array_equal(g[r + "cap9_n_steps"], ours["n_steps"]) and (ours["n_steps"] <= 9).all()
+    theirs, ours = g["trace_far_index"], geo.trace(pos[:4] * 3.0, d[:4], local_range=1.0)
+    assert (theirs[:, 0] == -1).all() and np.array_equal(theirs, ours["index"])
 
 
-def test_walks_equal_bit_for_bit_and_the_client_memo_quirk(tmp_path):
-    """C5's shape in small, live against the reference: scattering walks (a new direction at every
+def test_walks_equal_bit_for_bit_and_the_client_memo_quirk(golden):
+    """C5's shape in small, against the reference: scattering walks (a new direction at every
     step) over a mosaic that TOUCHES LONGITUDE 0, from 20 km up so that thousands of rays leave it.
     Through a stack without lock / unlock (the stepper looks the stack up itself) the restatement
     and the reference agree bit for bit on every ray -- medium, step count, path length.
@@ -57,15 +67,12 @@ def test_walks_equal_bit_for_bit_and_the_client_memo_quirk(tmp_path):
     rays).  Pinned here so that nobody mistakes it for a parity gap: every ray that differs under a
     locked stack is one that left the mosaic, and the unlocked reference sides with the restatement."""
     import philox_ref as P
-    n, K, N = 6000, 48, 1201
-    tiles = [(45, 0), (45, 1)]
-    d = str(tmp_path / "tiles")
-    for la, lo in tiles:
-        synth.write_hgt(d, la, lo, N)
-    geo = T.mosaic_oracle(tiles, N, 45, 0, 1, 2)
-    lat, lon, _, _ = synth.uniform_rays(n, (45.0, 46.0), (0.0, 2.0), seed=5)
-    pos, _ = geo.position(lat, lon, np.full(n, 20000.0))
+    g = golden("vs_reference")
+    n, K = N_RAYS, WALK_STEPS
+    geo = T.mosaic_oracle(WALK_TILES, N_NODES, 45, 0, 1, 2)
+    pos = g["walk_position"]
     dirs = np.stack([P.isotropic(n, 7, k) for k in range(K)])
+    assert T.sha(dirs) == str(g["walk_directions_sha"])
     ref_pos, total, taken = pos.copy(), np.zeros(n), np.zeros(n, dtype=np.int64)
     o = geo.step(ref_pos)
     alive = o["index"][:, 0] >= 0
@@ -77,10 +84,10 @@ def test_walks_equal_bit_for_bit_and_the_client_memo_quirk(tmp_path):
         alive &= o["index"][:, 0] >= 0
     medium = np.where(alive, o["index"][:, 0], -1)
     assert 500 < (taken < K).sum() < n                 # rays did leave, not all of them
-    free = R.stack_run(d, pos, dirs, walk_steps=K, local_range=0.0, locked=False)
+    free = {k: g["walk_free_" + k] for k in ("index", "n_steps", "length")}
     assert np.array_equal(free["index"][:, 0], medium) and np.array_equal(free["n_steps"], taken)
     assert np.array_equal(free["length"], total)        # bit for bit, every ray
-    locked = R.stack_run(d, pos, dirs, walk_steps=K, local_range=0.0, threads=1, locked=True)
+    locked = {k: g["walk_locked_" + k] for k in ("index", "n_steps", "length")}
     differs = locked["length"] != total
     assert 0 < differs.sum() < n                        # the quirk is there ...
     # ... and only ever takes steps away: a ray is located leaving the mosaic too early, or -- the
