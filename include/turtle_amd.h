@@ -485,10 +485,53 @@ TURTLE_API enum turtle_return turtle_stepper_trace_n(
     int * index /* [n][2] */, double * length, int * n_steps, int flags,
     int space);
 
-/* Totals of the LAST trace_n or scatter_n call on this stepper, accumulated on the
- * device: stats[0] rays, [1] steps, [2] samples (transform + layer lookup; the
- * same from run to run), [3] rays that stopped at max_steps.  Synchronises the
- * stream. */
+/* Number of media of the stepper's geometry: its layers + 1 (index[0] ranges
+ * over [0, media)). */
+TURTLE_API int turtle_amd_stepper_media(const struct turtle_stepper * stepper);
+
+/* Lines of sight: the rock length along each ray, every medium it meets, in one
+ * call.  For each ray r, exactly what this loop does with a fresh stepper history
+ * per ray [the loop of the reference's examples/example-stepper.c:128-140]:
+ *
+ *     turtle_stepper_step(s, pos, NULL, NULL, NULL, &alt, NULL, NULL, idx);
+ *     while (idx[0] >= 0 && alt < altitude_max && steps < max_steps) {
+ *             const int m = idx[0];
+ *             turtle_stepper_step(s, pos, dir, NULL, NULL, &alt, NULL, &ds, idx);
+ *             length[m * n + r] += ds;  steps++;  if (idx[0] != m) crossings++;
+ *     }
+ *
+ * The one departure from the reference's loop is the test idx[0] >= 0: its loop
+ * never ends on a ray that leaves the data (a step from outside returns ds = 0
+ * with the altitude unchanged).  altitude_max = HUGE_VAL: until the data ends or
+ * max_steps.  A ray that starts outside the data, or at or above the ceiling,
+ * takes 0 steps and reports the sample at its origin.  Outputs: position advanced
+ * in place; index[r] the final sample's pair; length medium-major, [media][n]
+ * (turtle_amd_stepper_media), each medium's column contiguous (it can go to
+ * turtle_amd_tally_n as it is), each sum accumulated step by step in the loop's
+ * order; n_steps and n_crossings per ray.  length, n_steps and n_crossings may be
+ * NULL: which outputs a caller asks for changes no bit of the others.
+ * turtle_stepper_trace_stats reports the call.  n <= 0 does nothing.
+ * Each crossing is located by HALVING the step's bracket, as the reference does,
+ * in either arithmetic (turtle_amd_math_set).  STRICT: the reference's arithmetic,
+ * up to the last ulp of asin/acos/atan2.  WHAT IS GUARANTEED in both (and tested
+ * against the reference's golden vectors and the CPU restatement at full size):
+ * the same final medium; the same step and crossing counts and every per-medium
+ * length within 1e-6 of the ray's total path, except on a ray that grazes a
+ * surface or cuts a sliver of it thinner than its step, where an ulp decides a
+ * sample (measured: 2 of 2e5 C2 rays on the sin.cos tile, ~40 of 2e5 on a rough
+ * tile with 200 m of node-to-node noise; DESIGN.md 3.7 and the test name them).
+ * Over stacks with tiles to page in, the rays go generation by generation over
+ * the step kernels (same bits in STRICT). */
+TURTLE_API enum turtle_return turtle_stepper_traverse_n(
+    struct turtle_stepper * stepper, long n, double * position /* [n][3], in / out */,
+    const double * direction /* [n][3] */, double altitude_max, int max_steps,
+    int * index /* [n][2], out: final */, double * length /* [media][n] or NULL */,
+    int * n_steps /* [n] or NULL */, int * n_crossings /* [n] or NULL */, int space);
+
+/* Totals of the LAST trace_n, scatter_n or traverse_n call on this stepper,
+ * accumulated on the device: stats[0] rays, [1] steps, [2] samples (transform +
+ * layer lookup; the same from run to run), [3] rays that stopped at max_steps.
+ * Synchronises the stream. */
 TURTLE_API enum turtle_return turtle_stepper_trace_stats(
     struct turtle_stepper * stepper, unsigned long long stats[4]);
 

@@ -597,6 +597,32 @@ class Stepper:
                                             _ptr(nsteps), flags, sp))
         return dict(position=pos, index=index, length=length, n_steps=nsteps)
 
+    @property
+    def media(self):
+        """turtle_amd_stepper_media: layers + 1"""
+        return int(lib().turtle_amd_stepper_media(self.h))
+
+    def traverse(self, position, direction, altitude_max=float("inf"), max_steps=1000000,
+                 want=("length", "n_steps", "n_crossings")):
+        """turtle_stepper_traverse_n: each ray stepped through every medium it meets until it
+        leaves the data, reaches `altitude_max` or has taken `max_steps` steps.  `length` has
+        shape (media, n): the path of each ray summed per medium.  The position advances in
+        place (as in trace)."""
+        sp = _space_of(position, direction)
+        pos = _as(position, sp).reshape(-1, 3)
+        d = _as(direction, sp).reshape(-1, 3)
+        n = pos.shape[0]
+        index = _new((n, 2), sp, np.int32, like=pos)
+        length = _new((self.media, n), sp, like=pos) if "length" in want else None
+        nsteps = _new((n,), sp, np.int32, like=pos) if "n_steps" in want else None
+        ncross = _new((n,), sp, np.int32, like=pos) if "n_crossings" in want else None
+        _check(lib().turtle_stepper_traverse_n(self.h, C.c_long(n), _ptr(pos), _ptr(d),
+                                               C.c_double(altitude_max), int(max_steps),
+                                               _ptr(index), _ptr(length), _ptr(nsteps),
+                                               _ptr(ncross), sp))
+        return dict(position=pos, index=index, length=length, n_steps=nsteps,
+                    n_crossings=ncross)
+
     def trace_into(self, pos, d, index, length, nsteps, max_steps=100000):
         """Device-resident trace with caller-owned tensors (no allocation):
         the timed call of bench.py."""

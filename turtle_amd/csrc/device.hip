@@ -1710,8 +1710,9 @@ __device__ __forceinline__ void step_items(const tamd_view & v, long n,
                  * taken instead of when the next step begins: the same bits. */
                 const bool compact = (flags & TAMD_STEP_COMPACT) != 0;
                 double ds_given = -1.;
-                /* a walk: a ray that has left the data takes no further step */
-                if (walk.on && (r >= 0) && (index[2 * r] < 0)) r = -1;
+                /* a walk: a ray that has left the data takes no further step (nor does a
+                 * ray a paged traverse has finished) */
+                if ((walk.on || (flags & TAMD_STEP_LIVE)) && (r >= 0) && (index[2 * r] < 0)) r = -1;
                 if (r >= 0) {
                 double px = pos[3 * r], py = pos[3 * r + 1], pz = pos[3 * r + 2];
                 Sample s;
@@ -3316,6 +3317,199 @@ __global__ void __launch_bounds__(256) WALK_WAVES_ATTR k_walk(tamd_view v, long 
         block_tally(stats, my_rays, my_steps, my_samples, my_plain);
 }
 
+/* ---- a line of sight per ray ------------------------------------------------
+ *
+ * turtle_stepper_traverse_n over a geometry with every tile resident: the loop
+ * of examples/example-stepper.c:128-140 [ref], one ray per lane from its origin
+ * sample to its last step.  k_walk's state machine (one sample per live lane and
+ * trip, STEP and BISECT bookkeeping as selects, the crossing located by halving
+ * and the ray going on in the new medium from the bisection's last sample) with
+ * a fixed direction, a third state for the origin sample (ST_INIT: q = B), the
+ * ceiling compared with the altitude turtle_stepper_step publishes (the step's
+ * sample after an accepted step, b_alt after a located crossing), and the path
+ * summed per medium: the running sum of the medium the ray is in is kept in a
+ * register, stored to length[m][r] when a crossing is located and the new
+ * medium's total loaded from length[m'][r] -- one load and one store a crossing,
+ * the reference's order of additions, and registers independent of the number
+ * of media.  Every lane ends through max_steps, the halving guard or the queue
+ * running dry. */
+struct TraverseIO {
+        const double * __restrict__ dir;
+        double * __restrict__ length; /* [media][n], zeroed by the driver; or NULL */
+        int * __restrict__ n_steps;   /* or NULL */
+        int * __restrict__ n_cross;   /* or NULL */
+        double ceiling;
+        int max_steps;
+};
+
+template <int MODE, bool FAST>
+__global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * __restrict__ pos,
+    int * __restrict__ index, TraverseIO io, ull * __restrict__ stats, ull * __restrict__ queue)
+{
+        long pool_next = 0, pool_end = 0; /* wave-uniform */
+        bool exhausted = false;            /* wave-uniform */
+        OneCtx ctx;
+        d_load_ctx<MODE, FAST>(v, ctx);
+        CellCache cell = { ~0u, 0u, 0u, -1, nullptr };
+        CellCache * cache = (FAST && (MODE != TAMD_MODE_GENERIC)) ? &cell : nullptr;
+
+        long ray = -1;
+        bool dead = false;
+        int state = ST_INIT, count = 0, crossings = 0;
+        double bx = 0, by = 0, bz = 0, dx = 0, dy = 0, dz = 0, len = 0;
+        double ds = 0, ds0 = 0, ds1 = 0;
+        double s_alt = 0, s_e0 = 0, s_e1 = 0; /* the sample the ray stands on */
+        double b_alt = 0, b_e0 = 0, b_e1 = 0; /* the bisection's last sample of the new medium */
+        int m = -1, k = -1, bm = -1, bk = -1, halvings = 0;
+        ull my_rays = 0, my_steps = 0, my_samples = 0, my_capped = 0;
+
+        for (;;) {
+                /* ---- refill idle lanes from the queue (as k_walk) ---- */
+                for (;;) {
+                        const bool need = (ray < 0) && !dead;
+                        const ull mask = __ballot(need);
+                        if (mask == 0) break;
+                        if (pool_next >= pool_end) {
+                                if (exhausted) {
+                                        if (need) dead = true;
+                                        break;
+                                }
+                                ull base = 0;
+                                if ((threadIdx.x & 63) == 0) base = atomicAdd(queue, (ull)kChunk);
+                                base = __shfl(base, 0, 64);
+                                pool_next = (long)base;
+                                pool_end = min((long)base + kChunk, n);
+                                if ((long)base >= n) {
+                                        exhausted = true;
+                                        pool_next = pool_end = 0;
+                                }
+                                continue;
+                        }
+                        const long avail = pool_end - pool_next;
+                        const int rank = __builtin_amdgcn_mbcnt_hi(
+                            (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+                        if (need && (rank < avail)) {
+                                ray = pool_next + rank;
+                                bx = pos[3 * ray], by = pos[3 * ray + 1], bz = pos[3 * ray + 2];
+                                dx = io.dir[3 * ray], dy = io.dir[3 * ray + 1], dz = io.dir[3 * ray + 2];
+                                state = ST_INIT, count = 0, crossings = 0, len = 0.;
+                        }
+                        pool_next += min((long)__popcll(mask), avail);
+                }
+                if (__ballot(ray >= 0) == 0) break; /* (a lane that drew nothing is dead: so are all) */
+                if (ray >= 0) {
+                        /* ---- one sample at q = B + d * t (the origin itself first) ---- */
+                        const bool init = (state == ST_INIT);
+                        const bool stepping = (state == ST_STEP);
+                        const double t = stepping ? ds : 0.5 * (ds0 + ds1);
+                        const double qx = init ? bx : bx + dx * t, qy = init ? by : by + dy * t,
+                                     qz = init ? bz : bz + dz * t;
+                        Sample s;
+                        d_sample<MODE, FAST>(v, ctx, qx, qy, qz, s, cache);
+                        my_samples++;
+                        bool ended = false;
+                        if (init) { /* [ref stepper.c:780-796] the loop's first call */
+                                m = s.m, k = s.k;
+                                s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
+                                state = ST_STEP;
+                                ended = true;
+                        } else {
+                                /* ---- bookkeeping: STEP and BISECT together, as selects (k_walk) ---- */
+                                const bool same = (s.m == m);
+                                const bool accept = stepping & same;
+                                const bool cross = stepping & !same;
+                                const bool other = !same;
+                                bx = stepping ? qx : bx, by = stepping ? qy : by, bz = stepping ? qz : bz;
+                                bm = other ? s.m : bm, bk = other ? s.k : bk;
+                                b_alt = other ? s.alt : b_alt, b_e0 = other ? s.e0 : b_e0, b_e1 = other ? s.e1 : b_e1;
+                                ds0 = cross ? -ds : ((!stepping & same) ? t : ds0);
+                                ds1 = cross ? 0. : ((!stepping & other) ? t : ds1);
+                                halvings = stepping ? 0 : halvings + 1;
+                                state = cross ? ST_BISECT : state;
+                                my_steps += stepping ? 1 : 0;
+                                const bool located = (state == ST_BISECT) & !cross &
+                                    (!(ds1 - ds0 > 1E-08) | (halvings > 1200));
+                                ended = accept;
+                                if (accept) {
+                                        len += ds, k = s.k;
+                                        s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
+                                }
+                                if (located) { /* [ref stepper.c:861-863] */
+                                        bx = bx + dx * ds1, by = by + dy * ds1, bz = bz + dz * ds1;
+                                        len += ds + ds1;
+                                        /* the sum of the medium left goes out, the new one's comes in */
+                                        if (io.length != nullptr) {
+                                                io.length[(long)m * n + ray] = len;
+                                                len = (bm >= 0) ? io.length[(long)bm * n + ray] : 0.;
+                                        }
+                                        m = bm, k = bk;
+                                        s_alt = b_alt, s_e0 = b_e0, s_e1 = b_e1;
+                                        crossings++;
+                                        state = ST_STEP;
+                                        ended = true;
+                                }
+                                count += ended ? 1 : 0;
+                        }
+                        if (ended) { /* a step is over (or the origin sampled): the loop's test */
+                                const bool low = (m >= 0) && (s_alt < io.ceiling);
+                                if (!low || (count >= io.max_steps)) {
+                                        pos[3 * ray] = bx, pos[3 * ray + 1] = by, pos[3 * ray + 2] = bz;
+                                        index[2 * ray] = m, index[2 * ray + 1] = k;
+                                        if ((io.length != nullptr) && (m >= 0)) io.length[(long)m * n + ray] = len;
+                                        if (io.n_steps != nullptr) io.n_steps[ray] = count;
+                                        if (io.n_cross != nullptr) io.n_cross[ray] = crossings;
+                                        my_rays++;
+                                        my_capped += low ? 1 : 0;
+                                        ray = -1;
+                                } else {
+                                        ds = d_step_length(v, s_alt, s_e0, s_e1, m);
+                                }
+                        }
+                }
+        }
+        block_tally(stats, my_rays, my_steps, my_samples, my_capped);
+}
+
+/* After one generation of a paged traverse (or, `first`, after the origins were
+ * sampled): the step each live ray took added to the sum of the medium it
+ * started in, the loop's test, and the rays it ends taken out of the stepping
+ * (live_index[r][0] = -1; their results are in index).  medium[r]: the medium a
+ * live ray is in, -1 once it is done. */
+__global__ void k_traverse_gen(long n, int first, const double * __restrict__ alt,
+    const double * __restrict__ step, int * __restrict__ live_index, int * __restrict__ medium,
+    int * __restrict__ index, double * __restrict__ length, int * __restrict__ n_steps,
+    int * __restrict__ n_cross, double ceiling, int max_steps, ull * __restrict__ counters)
+{
+        ull my_rays = 0, my_steps = 0, my_capped = 0, my_live = 0;
+        for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
+             r += (long)gridDim.x * blockDim.x) {
+                const int m1 = live_index[2 * r];
+                int count = 0;
+                if (first) {
+                        n_steps[r] = 0, n_cross[r] = 0;
+                } else {
+                        const int m0 = medium[r];
+                        if (m0 < 0) continue; /* done earlier */
+                        if (length != nullptr) length[(long)m0 * n + r] += step[r];
+                        count = n_steps[r] + 1;
+                        n_steps[r] = count;
+                        n_cross[r] += (m1 != m0) ? 1 : 0;
+                        my_steps++;
+                }
+                index[2 * r] = m1, index[2 * r + 1] = live_index[2 * r + 1];
+                const bool low = (m1 >= 0) && (alt[r] < ceiling);
+                if (!low || (count >= max_steps)) {
+                        medium[r] = -1, live_index[2 * r] = -1;
+                        my_rays++;
+                        my_capped += low ? 1 : 0;
+                } else {
+                        medium[r] = m1;
+                        my_live++;
+                }
+        }
+        block_tally(counters, my_rays, my_steps, my_capped, my_live);
+}
+
 __global__ void k_philox(long n, ull seed, ull stream, long first, unsigned * __restrict__ out)
 {
         for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
@@ -4334,6 +4528,70 @@ extern "C" int tamd_k_walk(struct tamd_view view, long n, double * pos, double *
                 WALK_CASE(TAMD_MODE_GENERIC);
 #undef WALK_CASE
         LAUNCH_CHECK("k_walk");
+        return 0;
+}
+
+/* A whole traverse in one launch (k_traverse): every tile resident, nothing listed */
+extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, const double * dir,
+    double ceiling, int max_steps, int * index, double * length, int * n_steps, int * n_cross,
+    unsigned long long * stats, unsigned long long * queue)
+{
+        if (tamd_dev_init()) return 1;
+        HIP_TRY(hipMemsetAsync(stats, 0, 4 * sizeof(ull), g_stream));
+        HIP_TRY(hipMemsetAsync(queue, 0, sizeof(ull), g_stream));
+        if (n <= 0) return 0;
+        const TraverseIO io = { dir, length, n_steps, n_cross, ceiling, max_steps };
+        const bool strict = g_math_strict || !view.fast_ok;
+#define TRAVERSE_CASE(MODE)                                                                    \
+        do {                                                                                   \
+                const void * kernel = strict ? (const void *)k_traverse<MODE, false> :        \
+                                               (const void *)k_traverse<MODE, true>;           \
+                long blocks = (long)g_cus * trace_blocks_per_cu(kernel);                       \
+                const long useful = (n + 255) / 256;                                           \
+                if (blocks > useful) blocks = useful;                                          \
+                if (strict)                                                                    \
+                        hipLaunchKernelGGL((k_traverse<MODE, false>), dim3((unsigned)blocks), dim3(256), 0, \
+                            g_stream, view, n, pos, index, io, stats, queue);                  \
+                else                                                                           \
+                        hipLaunchKernelGGL((k_traverse<MODE, true>), dim3((unsigned)blocks), dim3(256), 0,  \
+                            g_stream, view, n, pos, index, io, stats, queue);                  \
+        } while (0)
+        if (view.mode == TAMD_MODE_ONE_MAP)
+                TRAVERSE_CASE(TAMD_MODE_ONE_MAP);
+        else if (view.mode == TAMD_MODE_ONE_STACK)
+                TRAVERSE_CASE(TAMD_MODE_ONE_STACK);
+        else
+                TRAVERSE_CASE(TAMD_MODE_GENERIC);
+#undef TRAVERSE_CASE
+        LAUNCH_CHECK("k_traverse");
+        return 0;
+}
+
+/* One generation of a paged traverse: as tamd_k_step_dir with TURTLE_AMD_STEP_RESUME, the
+ * finished rays (index[r][0] = -1) left out; stats add up over the generations */
+extern "C" int tamd_k_step_live(struct tamd_view view, long n, double * pos, const double * dir,
+    double * alt, double * elev, double * step, int * index, int * cross_ray, double * cross_ds,
+    struct tamd_paging pg, unsigned long long * stats, unsigned long long * queue)
+{
+        if (tamd_dev_init()) return 1;
+        HIP_TRY(hipMemsetAsync(queue, 0, 3 * sizeof(ull), g_stream));
+        if (n <= 0) return 0;
+        const CrossList cross = { cross_ray, (cross_ray != nullptr) ? cross_ds : nullptr, queue + 2, nullptr };
+        const StepWalk no_walk = { 0, 0, 0, 0, nullptr, nullptr };
+        return run_step(view, n, pos, dir, nullptr, nullptr, alt, elev, step, index,
+            TURTLE_AMD_STEP_RESUME | TAMD_STEP_LIVE, cross, pg, stats, no_walk);
+}
+
+extern "C" int tamd_k_traverse_gen(long n, int first, const double * alt, const double * step,
+    int * live_index, int * medium, int * index, double * length, int * n_steps, int * n_cross,
+    double ceiling, int max_steps, unsigned long long * counters)
+{
+        if (tamd_dev_init()) return 1;
+        if (n <= 0) return 0;
+        hipLaunchKernelGGL(k_traverse_gen, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, n, first,
+            alt, step, live_index, medium, index, length, n_steps, n_cross, ceiling, max_steps,
+            counters);
+        LAUNCH_CHECK("k_traverse_gen");
         return 0;
 }
 

@@ -251,6 +251,28 @@ int tamd_k_step_walk(struct tamd_view view, long n, double * pos, double * alt,
 int tamd_k_walk(struct tamd_view view, long n, double * pos, double * alt, double * elev,
     int * index, unsigned long long seed, long first, int first_step, int n_steps, double * length,
     int * steps, unsigned long long * stats, unsigned long long * queue);
+/* a flag of the step kernels: a ray whose index[r][0] is -1 takes no step and is left as it is (the
+ * rays a paged turtle_stepper_traverse_n has finished) */
+#define TAMD_STEP_LIVE 0x400
+/* turtle_stepper_traverse_n, every tile resident: each ray sampled at its origin, then stepped
+ * along dir until it leaves the data, reaches `ceiling` or has taken max_steps steps, its path
+ * length summed per medium into length[m * n + r] (zeroed by the caller; or NULL); n_steps and
+ * n_cross may be NULL.  stats (rays, steps, samples, rays stopped by max_steps) and queue[0] are
+ * zeroed by the launcher. */
+int tamd_k_traverse(struct tamd_view view, long n, double * pos, const double * dir,
+    double ceiling, int max_steps, int * index, double * length, int * n_steps, int * n_cross,
+    unsigned long long * stats, unsigned long long * queue);
+/* the generation-by-generation form over paged stacks: one step of every ray whose index[r][0]
+ * >= 0, resumed from alt / elev / index (tamd_k_step_dir with TURTLE_AMD_STEP_RESUME |
+ * TAMD_STEP_LIVE; stats NOT zeroed); then tamd_k_traverse_gen adds what it took to the sums.
+ * first != 0: no step was taken yet, the outputs are set from the origin's sample. counters:
+ * rays finished, steps, rays stopped by max_steps, rays still live (the caller zeroes [3]). */
+int tamd_k_step_live(struct tamd_view view, long n, double * pos, const double * dir,
+    double * alt, double * elev, double * step, int * index, int * cross_ray, double * cross_ds,
+    struct tamd_paging pg, unsigned long long * stats, unsigned long long * queue);
+int tamd_k_traverse_gen(long n, int first, const double * alt, const double * step, int * live_index,
+    int * medium, int * index, double * length, int * n_steps, int * n_cross, double ceiling,
+    int max_steps, unsigned long long * counters);
 int tamd_k_philox(long n, unsigned long long seed, unsigned long long stream,
     long first, unsigned * out);
 int tamd_k_isotropic(long n, unsigned long long seed, unsigned long long stream,

@@ -957,6 +957,150 @@ enum turtle_return turtle_stepper_trace_n(struct turtle_stepper * stepper, long 
         return TURTLE_RETURN_SUCCESS;
 }
 
+/* ---- lines of sight --------------------------------------------------------- */
+
+int turtle_amd_stepper_media(const struct turtle_stepper * stepper) { return stepper->n_layers + 1; }
+
+struct traverse_args {
+        long n;
+        void *pos, *dir, *alt, *elev, *step, *live;
+};
+
+static int traverse_start_round(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
+{
+        struct traverse_args * a = p;
+        (void)round;
+        return tamd_k_step(stepper->view, a->n, a->pos, NULL, NULL, NULL, a->alt, a->elev, NULL,
+            a->live, 0, pg);
+}
+
+static int traverse_round(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
+{
+        struct traverse_args * a = p;
+        (void)round;
+        return tamd_k_step_live(stepper->view, a->n, a->pos, a->dir, a->alt, a->elev, a->step, a->live,
+            stepper->d_parked, stepper->d_scratch_ds, pg, stepper->d_stats + 4 + 4, stepper->d_stats + 4);
+}
+
+static void * traverse_piece(char * block, size_t * used, size_t bytes)
+{
+        void * piece = block + *used;
+        *used += ((bytes + 255) / 256) * 256;
+        return piece;
+}
+
+/* Over paged stacks: generation by generation over the step kernels, each in rounds over the rays
+ * that wait for a tile (as scatter_n), the sums kept by k_traverse_gen.  The same arithmetic on the
+ * same values as k_traverse in STRICT: the same bits. */
+static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos, const double * dir,
+    double ceiling, int max_steps, int * index, double * length, int * n_steps, int * n_cross,
+    char * message, size_t size)
+{
+        /* the sample state between generations, and the counts the caller may not want */
+        const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int);
+        const size_t bytes = 4 * nb + 5 * ni + 4 * sizeof(unsigned long long) + 7 * 256;
+        char * block;
+        if (tamd_dev_malloc((void **)&block, bytes)) return TURTLE_RETURN_LIBRARY_ERROR;
+        size_t used = 0;
+        struct traverse_args a = { n, pos, (void *)dir, NULL, NULL, NULL, NULL };
+        a.alt = traverse_piece(block, &used, nb);
+        a.elev = traverse_piece(block, &used, 2 * nb);
+        a.step = traverse_piece(block, &used, nb);
+        a.live = traverse_piece(block, &used, 2 * ni);
+        int * medium = traverse_piece(block, &used, ni);
+        int * own = traverse_piece(block, &used, 2 * ni);
+        unsigned long long * counters = traverse_piece(block, &used, 4 * sizeof(unsigned long long));
+        if (n_steps == NULL) n_steps = own;
+        if (n_cross == NULL) n_cross = own + n;
+        /* counters: [0, 4) k_traverse_gen's; the step kernels' stats are in d_stats[8, 12) */
+        int rc = stepper_rounds(stepper, n, &traverse_start_round, &a, message, size);
+        int rounds = stepper->last_rounds; /* (turtle_amd_stepper_rounds: the most a generation took) */
+        if ((rc == 0) && (tamd_dev_zero(counters, 4 * sizeof(*counters)) ||
+                             tamd_dev_zero(stepper->d_stats + 8, 4 * sizeof(*stepper->d_stats)) ||
+                             tamd_k_traverse_gen(n, 1, a.alt, NULL, a.live, medium, index, length,
+                                 n_steps, n_cross, ceiling, max_steps, counters)))
+                rc = TURTLE_RETURN_LIBRARY_ERROR;
+        unsigned long long c[4] = { 0, 0, 0, 0 };
+        while (rc == 0) { /* (a generation ends a ray or takes a step of it: max_steps bounds the loop) */
+                if (tamd_dev_d2h(c, counters, sizeof(c))) {
+                        rc = TURTLE_RETURN_LIBRARY_ERROR;
+                        break;
+                }
+                if (c[3] == 0) break; /* no ray left live */
+                if (tamd_dev_zero(counters + 3, sizeof(*counters))) {
+                        rc = TURTLE_RETURN_LIBRARY_ERROR;
+                        break;
+                }
+                rc = stepper_rounds(stepper, n, &traverse_round, &a, message, size);
+                if (stepper->last_rounds > rounds) rounds = stepper->last_rounds;
+                if ((rc == 0) && tamd_k_traverse_gen(n, 0, a.alt, a.step, a.live, medium, index, length,
+                                     n_steps, n_cross, ceiling, max_steps, counters))
+                        rc = TURTLE_RETURN_LIBRARY_ERROR;
+        }
+        /* turtle_stepper_trace_stats: rays, steps, samples (the origins' and the step kernels'),
+         * rays stopped by max_steps */
+        unsigned long long taken[4];
+        if ((rc == 0) && tamd_dev_d2h(taken, stepper->d_stats + 8, sizeof(taken))) rc = TURTLE_RETURN_LIBRARY_ERROR;
+        if (rc == 0) {
+                const unsigned long long stats[4] = { c[0], c[1], (unsigned long long)n + taken[2], c[2] };
+                if (tamd_dev_h2d(stepper->d_stats, stats, sizeof(stats))) rc = TURTLE_RETURN_LIBRARY_ERROR;
+        }
+        stepper->last_rounds = rounds;
+        tamd_dev_sync();
+        tamd_dev_free(block);
+        return rc;
+}
+
+enum turtle_return turtle_stepper_traverse_n(struct turtle_stepper * stepper, long n,
+    double * position, const double * direction, double altitude_max, int max_steps, int * index,
+    double * length, int * n_steps, int * n_crossings, int space)
+{
+        TAMD_ERROR_INIT(&turtle_stepper_traverse_n);
+        if ((position == NULL) || (direction == NULL) || (index == NULL))
+                return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
+        if (max_steps < 0) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid input parameter(s)");
+        if (n <= 0) return TURTLE_RETURN_SUCCESS;
+        char message[4200];
+        int rc = tamd_stepper_flatten(stepper, message, sizeof(message));
+        if (rc < 0) return TAMD_RAISE_DEVICE();
+        if (rc > 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
+        const int paged = stepper_is_paged(stepper);
+        if (paged && (tamd_stepper_scratch(stepper, n) != 0)) {
+                if (stepper->parked_capacity < 0) return TAMD_RAISE_DEVICE();
+                return TAMD_RAISE(TURTLE_RETURN_MEMORY_ERROR, "batch too large");
+        }
+        const long media = stepper->n_layers + 1;
+        struct tamd_stage st;
+        void *dp, *dd, *dix, *dlen, *dst, *dcr;
+        const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int);
+        if (tamd_stage_begin(&st, space, (6 + media) * nb + 4 * ni) ||
+            tamd_stage_in(&st, position, 3 * nb, &dp) || tamd_stage_in(&st, direction, 3 * nb, &dd) ||
+            tamd_stage_out(&st, index, 2 * ni, &dix) || tamd_stage_out(&st, length, media * nb, &dlen) ||
+            tamd_stage_out(&st, n_steps, ni, &dst) || tamd_stage_out(&st, n_crossings, ni, &dcr))
+                return TAMD_RAISE_DEVICE();
+        /* the sums are added to where they stand: they start from zero */
+        if ((dlen != NULL) && tamd_dev_zero(dlen, media * nb)) return TAMD_RAISE_DEVICE();
+        if (!paged) { /* every tile resident: the whole traverse in one launch */
+                tamd_geometry_use_begin();
+                rc = tamd_stepper_flatten(stepper, message, sizeof(message));
+                if (rc < 0) rc = TURTLE_RETURN_LIBRARY_ERROR;
+                if ((rc == 0) && tamd_k_traverse(stepper->view, n, dp, dd, altitude_max, max_steps, dix,
+                                     dlen, dst, dcr, stepper->d_stats, stepper->d_stats + 4))
+                        rc = TURTLE_RETURN_LIBRARY_ERROR;
+                tamd_geometry_use_end();
+                stepper->last_rounds = 1;
+        } else
+                rc = traverse_paged(stepper, n, dp, dd, altitude_max, max_steps, dix, dlen, dst, dcr,
+                    message, sizeof(message));
+        if (rc == TURTLE_RETURN_LIBRARY_ERROR) return TAMD_RAISE_DEVICE();
+        if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
+        if (tamd_stage_fetch(&st, position, 3 * nb, dp) || tamd_stage_fetch(&st, index, 2 * ni, dix) ||
+            tamd_stage_fetch(&st, length, media * nb, dlen) || tamd_stage_fetch(&st, n_steps, ni, dst) ||
+            tamd_stage_fetch(&st, n_crossings, ni, dcr) || tamd_stage_end(&st))
+                return TAMD_RAISE_DEVICE();
+        return TURTLE_RETURN_SUCCESS;
+}
+
 int turtle_amd_stepper_rounds(const struct turtle_stepper * stepper) { return stepper->last_rounds; }
 
 enum turtle_return turtle_stepper_trace_stats(

@@ -113,3 +113,48 @@ def write_geotiff(directory: str, lat0: int, lon0: int, n: int = HGT_N) -> str:
     with open(path, "wb") as f:
         f.write(geotiff_bytes(srtm_like_nodes(lat0, lon0, n), float(lon0), float(lat0 + 1), step, step))
     return path
+
+
+def _hash32(x: np.ndarray, y: np.ndarray, salt: int) -> np.ndarray:
+    """A 32-bit integer hash of integer lattice coordinates (uint64 arithmetic, masked): the same
+    words on any platform and any numpy, which np.random does not promise across versions."""
+    m = np.uint64(0xFFFFFFFF)
+    h = (x.astype(np.uint64) * np.uint64(0x8DA6B343)) & m
+    h ^= (y.astype(np.uint64) * np.uint64(0xD8163841)) & m
+    h ^= np.uint64((salt * 0xCB1AB31F) & 0xFFFFFFFF)
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x7FEB352D)) & m
+    h ^= h >> np.uint64(15)
+    h = (h * np.uint64(0x846CA68B)) & m
+    h ^= h >> np.uint64(16)
+    return h
+
+
+def rough_nodes(n: int = 1201, seed: int = 1, amplitude: int = 800) -> np.ndarray:
+    """Rough ground on one tile, as int16 [row south->north, col west->east]: 1000 m plus five
+    octaves of integer value noise (lattice cells of 256 down to 16 nodes, bilinear weights in
+    integers, octave o weighing amplitude / 2^o) plus per-node noise in [-200, 200] m.  Every
+    value comes from an integer hash of (node or lattice point, seed): ridges and hollows at
+    every scale, so lines of sight cross the ground many times."""
+    iy, ix = np.meshgrid(np.arange(n, dtype=np.int64), np.arange(n, dtype=np.int64), indexing="ij")
+    z = np.full((n, n), 1000, dtype=np.int64)
+    for o, cell in enumerate((256, 128, 64, 32, 16)):
+        cx, cy = ix // cell, iy // cell
+        fx, fy = ix % cell, iy % cell
+        def lattice(dx, dy):
+            return (_hash32(cx + dx, cy + dy, 16 * seed + o) >> np.uint64(16)).astype(np.int64) - 32768
+        v = (lattice(0, 0) * (cell - fx) * (cell - fy) + lattice(1, 0) * fx * (cell - fy) +
+             lattice(0, 1) * (cell - fx) * fy + lattice(1, 1) * fx * fy) // (cell * cell)
+        z += (amplitude * v) // (32768 << o)
+    z += (_hash32(ix, iy, 16 * seed + 15) % np.uint64(401)).astype(np.int64) - 200
+    return np.clip(z, -32767, 32767).astype(np.int16)
+
+
+def write_rough_hgt(directory: str, lat0: int, lon0: int, n: int = 1201, seed: int = 1,
+                    amplitude: int = 800) -> str:
+    """rough_nodes as an .hgt tile named for (lat0, lon0)"""
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, hgt_name(lat0, lon0, n))
+    with open(path, "wb") as f:
+        f.write(hgt_bytes(rough_nodes(n, seed, amplitude)))
+    return path
