@@ -56,3 +56,14 @@ def mosaic_oracle(tiles, n, lat0, lon0, nlat, nlon):
     stack = dict(lat0=float(lat0), lon0=float(lon0), dlat=1.0, dlon=1.0,
                  nlat=nlat, nlon=nlon, tile=table)
     return O.OracleGeometry(grids=grids, stacks=[stack], layers=[[(O.STACK, 0, 0.0)]])
+
+
+def mosaic_oracle_nodes(tiles, lat0, lon0, nlat, nlon):
+    """mosaic_oracle over given node arrays: `tiles` maps (lat, lon) to int16 nodes [south->north]"""
+    grids, table = [], -np.ones((nlat, nlon), dtype=np.int32)
+    for (la, lo), nodes in tiles.items():
+        table[la - lat0, lo - lon0] = len(grids)
+        grids.append(O.hgt_grid(la, lo, nodes))
+    stack = dict(lat0=float(lat0), lon0=float(lon0), dlat=1.0, dlon=1.0,
+                 nlat=nlat, nlon=nlon, tile=table)
+    return O.OracleGeometry(grids=grids, stacks=[stack], layers=[[(O.STACK, 0, 0.0)]])

@@ -225,3 +225,35 @@ def test_g9_projected_map_in_the_stepper(golden):
         assert eq(o["step"], rows[:, 5]) and eq(o["index"], rows[:, 6:8].astype(np.int32))
         t = geo.trace(g[name + "_pos"], g[name + "_dir"])
         _check_trace(t, g, name + "_t")
+
+
+def test_g12_rough_and_void_ground(golden):
+    """Traces, single steps and deep ECEF -> geodetic over rough and void ground (tests/rough_cases.py):
+    the restatement against the reference, bit for bit -- the values stored in rough.npz, and the
+    origins, directions and positions against the sha256 of the reference's"""
+    import rough_cases as RC
+    g = golden("rough")
+    for case in RC.CASES:
+        assert RC.sha(RC.nodes(case)) == str(g[f"{case}_nodes_sha"])
+        geo = RC.oracle_geometry(case)
+        for recipe in RC.recipes(case):
+            k = f"{case}_{recipe}_"
+            pos, d = RC.oracle_rays(case, recipe)
+            assert RC.sha(pos) == str(g[k + "origin_sha"]) and RC.sha(d) == str(g[k + "direction_sha"])
+            t = geo.trace(pos, d, max_steps=1000000, threads=4)
+            assert eq(t["index"], g[k + "index"].astype(np.int32)), k
+            assert eq(t["n_steps"], g[k + "n_steps"]) and eq(t["length"], g[k + "length"]), k
+            assert RC.sha(t["position"]) == str(g[k + "position_sha"]), k
+        pos, d = RC.oracle_rays(case, "ground")
+        ds, index, position = RC.oracle_step_records(geo, pos[:RC.STEP_RAYS], d[:RC.STEP_RAYS])
+        assert RC.sha(ds) == str(g[f"{case}_steps_ds_sha"])
+        assert eq(index, g[f"{case}_steps_index"].astype(np.int32))
+        assert RC.sha(position) == str(g[f"{case}_steps_position_sha"])
+    # the void tile: rays that start in a void (32 km below the ellipsoid) and rays that end in one
+    lat, lon, _ = O.ecef_to_geodetic(RC.oracle_rays("void", "c2")[0])
+    z, _ = RC.oracle_geometry("void").grid_elevation(0, lon, lat)
+    assert (z < -30000).sum() >= 10
+    assert all((g[f"void_edge{k}_index"][:, 0] == 0).sum() > 30 for k in range(len(RC.VOID_BLOCKS)))
+    e, geodetic = RC.deep_transforms(O.ecef_from_geodetic, O.ecef_to_geodetic)
+    assert RC.sha(e) == str(g["deep_ecef_sha"]) and RC.sha(geodetic) == str(g["deep_geodetic_sha"])
+    assert (geodetic[2] < -25e3 + 1).all() and (geodetic[2] > -40e3 - 1).all()

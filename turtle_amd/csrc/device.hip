@@ -1235,27 +1235,51 @@ __device__ __forceinline__ bool f_sample_on_line(const tamd_view & v, const OneC
 }
 
 /* Where a fast trace samples next inside the bracket [ds0, ds1] of a crossing
- * [ref stepper.c:840-860 halves it, 27 times from a metre to 1e-8 m].  c0, c1:
- * the clearances (distance to the nearest boundary, >= 0) of the samples at its
- * two ends -- over a bracket of a metre or less both measure the same boundary:
- * the crossing is where they interpolate to zero (false position, with the
- * Illinois rule: the clearance of an end that has stayed put while the other moved
- * twice is halved, or a bent surface would keep every sample on one side).  The
- * sample is taken 0.4e-8 m to the side of that estimate whose end is the farther
- * one, so that once the estimate is good the two ends close in from both sides:
- * two such samples and the bracket is 0.8e-8 m wide, where the reference's test
- * ends it too, around the same crossing (both brackets hold it, both are below
- * 1e-8 m: the end points agree to that).  A bracket stays a bracket whatever the
- * estimate is worth (a cell's edge, another layer nearby, a first clearance that
- * was only guessed); after kBracketPatience samples the midpoint takes over. */
-constexpr int kBracketPatience = 24;
+ * [ref stepper.c:840-860 halves it, 27 times from a metre to 1e-8 m].
+ *
+ * While the bracket is wider than kBracketHalve, at its midpoint: the sample the
+ * reference takes, so that the trace takes the reference's decisions where the
+ * bracket may hold several crossings.  On rough ground it does: a step is 0.4 x
+ * the clearance below the ray, and ground that rises faster than that along the
+ * ray (a spike, a ridge thinner than the step, the wall of an HGT void) is crossed
+ * twice or more within it.  Halving and false position then end on different
+ * crossings, metres to kilometres apart -- on the rough tiles of
+ * tests/rough_cases.py, false position from the step's full bracket ended on
+ * another crossing than the reference for 55 of 10^4 rays of C2's recipe over the
+ * void tile and for up to 13 % of the rays aimed at a void's edge.
+ * Below kBracketHalve = 0.1 m the ground along the ray is one piece of a
+ * bilinear cell (a parabola in the ray's parameter) or two, joined at a cell's
+ * edge: to meet it twice within 0.1 m the ray has to pass within |f''| (0.05 m)^2
+ * of a hollow or crest of that parabola, or within |slope change| x 0.05 m of a
+ * cell's edge -- millimetres to centimetres on SRTM-like ground, decimetres on
+ * the 200 m per-node noise of the rough tile, where a replay of this rule over the
+ * oracle's samples found no such bracket among 44 000 rays: that is grazing, and
+ * there either answer is one.
+ *
+ * Below kBracketHalve: false position.  c0, c1: the clearances (distance to the
+ * nearest boundary, >= 0) of the samples at the two ends -- over a bracket this
+ * narrow both measure the same boundary: the crossing is where they interpolate
+ * to zero (with the Illinois rule: the clearance of an end that has stayed put
+ * while the other moved twice by false position is halved, or a bent surface
+ * would keep every sample on one side).  The sample is taken 0.4e-8 m to the side
+ * of that estimate whose end is the farther one, so that once the estimate is
+ * good the two ends close in from both sides: two such samples and the bracket is
+ * 0.8e-8 m wide, where the reference's test ends it too, around the same crossing
+ * (both brackets hold it, both are below 1e-8 m: the end points agree to that).
+ * A bracket stays a bracket whatever the estimate is worth (a cell's edge, another
+ * layer nearby, a first clearance that was only guessed); after kBracketPatience
+ * samples in all the midpoint takes over again. */
+constexpr double kBracketHalve = 0.1;
+constexpr int kBracketPatience = 64;
+__device__ __forceinline__ bool f_bracket_halves(double ds0, double ds1) { return ds1 - ds0 > kBracketHalve; }
 __device__ __forceinline__ double f_bracket_point(double ds0, double ds1, double c0, double c1,
     int taken)
 {
         const double w = ds1 - ds0;
         const double sum = c0 + c1;
         double t = 0.5 * (ds0 + ds1);
-        if ((taken < kBracketPatience) && (sum > 0.) && (sum < 1e30) && (w > 2.5e-8)) {
+        if ((taken < kBracketPatience) && !f_bracket_halves(ds0, ds1) && (sum > 0.) && (sum < 1e30) &&
+            (w > 2.5e-8)) {
                 const double r = ds0 + w * (c0 / sum);
                 const double aim = ((r - ds0) >= (ds1 - r)) ? r - 0.4e-8 : r + 0.4e-8;
                 t = fmin(fmax(aim, ds0 + 0.25e-8), ds1 - 0.25e-8);
@@ -2790,6 +2814,8 @@ __device__ __forceinline__ void trace_body(const tamd_view & v, long n,
                                 len = accept ? len + ds : len;
                                 k = accept ? s.k : k;
                                 bm = other ? s.m : bm, bk = other ? s.k : bk;
+                                /* the sample halved the bracket: the Illinois rule waits (f_bracket_point) */
+                                const bool halved = !CROSS && !stepping && f_bracket_halves(ds0, ds1);
                                 /* the bracket [ref stepper.c:836, :849-858] */
                                 ds0 = cross ? -ds : ((!stepping & same) ? t : ds0);
                                 ds1 = cross ? 0. : ((!stepping & other) ? t : ds1);
@@ -2802,7 +2828,7 @@ __device__ __forceinline__ void trace_body(const tamd_view & v, long n,
                                         const bool again1 = !stepping & other & ((halvings & 0x20000) != 0);
                                         c0 = cross ? ds / v.slope : ((!stepping & same) ? cl : (again1 ? 0.5 * c0 : c0));
                                         c1 = (cross | (!stepping & other)) ? cl : (again0 ? 0.5 * c1 : c1);
-                                        moved_twice = stepping ? 0 : (same ? 0x10000 : 0x20000);
+                                        moved_twice = (stepping | halved) ? 0 : (same ? 0x10000 : 0x20000);
                                 }
                                 ds = accept ? ds_next : ds; /* a crossing keeps the tentative length */
                                 count += accept ? 1 : 0;
@@ -3107,6 +3133,7 @@ __global__ void __launch_bounds__(256) k_cross(tamd_view v, double * __restrict_
                         double c1 = agreed ? fmin(fabs(s.alt - s.e0), fabs(s.alt - s.e1)) : 0.;
                         int taken = 0, last = 0; /* last: the end the previous sample moved (1: ds0, 2: ds1) */
                         while ((fault.centre < 0) && (ds1 - ds0 > 1E-08) && (taken <= 1200)) {
+                                const bool halving = f_bracket_halves(ds0, ds1); /* (no Illinois rule then) */
                                 const double t = FAST ? f_bracket_point(ds0, ds1, c0, c1, taken) :
                                                         0.5 * (ds0 + ds1);
                                 const double qx = d_along<FAST>(px, dx, t), qy = d_along<FAST>(py, dy, t), qz = d_along<FAST>(pz, dz, t);
@@ -3126,7 +3153,7 @@ __global__ void __launch_bounds__(256) k_cross(tamd_view v, double * __restrict_
                                         if (FAST) {
                                                 c0 = fmin(fabs(s2.alt - s2.e0), fabs(s2.alt - s2.e1));
                                                 if (last == 1) c1 = 0.5 * c1; /* the Illinois rule */
-                                                last = 1;
+                                                last = halving ? 0 : 1;
                                         }
                                 } else {
                                         ds1 = t;
@@ -3134,7 +3161,7 @@ __global__ void __launch_bounds__(256) k_cross(tamd_view v, double * __restrict_
                                         if (FAST) {
                                                 c1 = fmin(fabs(s2.alt - s2.e0), fabs(s2.alt - s2.e1));
                                                 if (last == 2) c0 = 0.5 * c0;
-                                                last = 2;
+                                                last = halving ? 0 : 2;
                                         }
                                 }
                         }

@@ -130,10 +130,10 @@ def _hash32(x: np.ndarray, y: np.ndarray, salt: int) -> np.ndarray:
     return h
 
 
-def rough_nodes(n: int = 1201, seed: int = 1, amplitude: int = 800) -> np.ndarray:
+def rough_nodes(n: int = 1201, seed: int = 1, amplitude: int = 800, noise: int = 200) -> np.ndarray:
     """Rough ground on one tile, as int16 [row south->north, col west->east]: 1000 m plus five
     octaves of integer value noise (lattice cells of 256 down to 16 nodes, bilinear weights in
-    integers, octave o weighing amplitude / 2^o) plus per-node noise in [-200, 200] m.  Every
+    integers, octave o weighing amplitude / 2^o) plus per-node noise in [-noise, noise] m.  Every
     value comes from an integer hash of (node or lattice point, seed): ridges and hollows at
     every scale, so lines of sight cross the ground many times."""
     iy, ix = np.meshgrid(np.arange(n, dtype=np.int64), np.arange(n, dtype=np.int64), indexing="ij")
@@ -146,8 +146,29 @@ def rough_nodes(n: int = 1201, seed: int = 1, amplitude: int = 800) -> np.ndarra
         v = (lattice(0, 0) * (cell - fx) * (cell - fy) + lattice(1, 0) * fx * (cell - fy) +
              lattice(0, 1) * (cell - fx) * fy + lattice(1, 1) * fx * fy) // (cell * cell)
         z += (amplitude * v) // (32768 << o)
-    z += (_hash32(ix, iy, 16 * seed + 15) % np.uint64(401)).astype(np.int64) - 200
+    z += (_hash32(ix, iy, 16 * seed + 15) % np.uint64(2 * noise + 1)).astype(np.int64) - noise
     return np.clip(z, -32767, 32767).astype(np.int16)
+
+
+VOID = -32768  # an HGT void [ref src/turtle/io/hgt.c reads it as an elevation, unmasked]
+
+
+def with_voids(nodes: np.ndarray, blocks) -> np.ndarray:
+    """A copy of int16 nodes [row south->north, col west->east] with each block (row0, row1, col0,
+    col1), half-open, set to the HGT void value"""
+    out = np.array(nodes, dtype=np.int16, copy=True)
+    for r0, r1, c0, c1 in blocks:
+        out[r0:r1, c0:c1] = VOID
+    return out
+
+
+def write_nodes_hgt(directory: str, lat0: int, lon0: int, nodes_s2n: np.ndarray) -> str:
+    """Any square int16 nodes [row south->north] as an .hgt tile named for (lat0, lon0)"""
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, hgt_name(lat0, lon0, nodes_s2n.shape[0]))
+    with open(path, "wb") as f:
+        f.write(hgt_bytes(nodes_s2n))
+    return path
 
 
 def write_rough_hgt(directory: str, lat0: int, lon0: int, n: int = 1201, seed: int = 1,
