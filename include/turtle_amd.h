@@ -378,6 +378,46 @@ TURTLE_API enum turtle_return turtle_stack_elevation_n(
     struct turtle_stack * stack, long n, const double * latitude,
     const double * longitude, double * elevation, int * inside, int space);
 
+/* Flags of turtle_map_resample. */
+enum turtle_amd_resample_flags {
+        /* an elevation outside the map's span is stored as the nearest end of the span
+         * instead of failing the call */
+        TURTLE_AMD_RESAMPLE_CLAMP = 1
+};
+
+/* Fills every node of `map` from `stack` or from another map `source` (exactly one of them):
+ * the loop of the reference's examples/example-projection.c as one call.  For every node
+ * (ix, iy) of the map it does exactly this:
+ *
+ *     x = x0 + ix*dx;  y = y0 + iy*dy;                       (turtle_map_node)
+ *     if map is projected: turtle_projection_unproject(proj(map), x, y, &lat, &lon);
+ *     else                 lat = y, lon = x;
+ *     if stack:  turtle_stack_elevation(stack, lat, lon, &z, &inside);
+ *     else: (u, v) = source has the SAME projection as map (same type and parameters,
+ *                    or both geographic) ? (x, y)
+ *                  : source projected ? turtle_projection_project(proj(source), lat, lon)
+ *                  : (lon, lat);
+ *           turtle_map_elevation(source, u, v, &z, &inside);
+ *     if (inside) turtle_map_fill(map, ix, iy, z);           (else the node keeps its value)
+ *
+ * One departure from the example: it fills the nodes that fall outside the data too (with
+ * the 0 its turtle_stack_elevation returns there); this call leaves them as they are and
+ * counts them in *outside.  Each node gets the 16-bit code turtle_map_fill stores for z.
+ * A z outside [z0, z0 + 65535 dz] (or z != z0 when dz <= 0; HGT voids among them) fails
+ * the call with DOMAIN_ERROR and turtle_map_fill's message, and then NO node changes, on
+ * the host or in any HBM copy; with TURTLE_AMD_RESAMPLE_CLAMP it is stored as the nearest
+ * end of the span and counted in *clamped.  Lookups are always the strict bilinear ones:
+ * the result does not depend on turtle_amd_math_set.  BAD_ADDRESS: map == NULL, or neither
+ * source; DOMAIN_ERROR: both sources, source == map, a map that is a tile of a stack, or
+ * unknown flags -- all of them change nothing.  Afterwards every reader sees the new
+ * nodes: turtle_map_node / _dump and the host path, the kernels, and steppers that hold
+ * the map already.  A paged stack is read in rounds, as the other batch calls do.
+ * outside, clamped: may be NULL.  A map in use by another thread is the caller's race, as
+ * with turtle_map_fill. */
+TURTLE_API enum turtle_return turtle_map_resample(struct turtle_map * map,
+    struct turtle_stack * stack /* or NULL */, const struct turtle_map * source /* or NULL */,
+    int flags, long * outside /* or NULL */, long * clamped /* or NULL */);
+
 /* n gradients (the surface normal a Monte-Carlo needs at a hit point).  The
  * output arrays are in-out, as in the scalar calls. */
 TURTLE_API enum turtle_return turtle_map_gradient_n(

@@ -18,6 +18,7 @@ HOST, DEVICE = 0, 1
 STEP_RESUME = 1
 TRACE_RESUME = 1
 SCATTER_START = 1
+RESAMPLE_CLAMP = 1
 
 RETURN_NAMES = [
     "SUCCESS", "BAD_ADDRESS", "BAD_EXTENSION", "BAD_FORMAT", "BAD_PROJECTION",
@@ -379,6 +380,17 @@ class Map:
         _check(lib().turtle_map_gradient_n(self.h, C.c_long(n), _ptr(x), _ptr(y), _ptr(gx),
                                            _ptr(gy), _ptr(inside), sp))
         return gx, gy, inside
+
+    def resample(self, stack=None, source=None, clamp=False):
+        """turtle_map_resample: every node from `stack` or from the map `source` (one of
+        them) -> (outside, clamped), the nodes left as they were for want of data and the
+        nodes clamped to the span."""
+        outside, clamped = C.c_long(0), C.c_long(0)
+        _check(lib().turtle_map_resample(self.h, stack.h if stack is not None else None,
+                                         source.h if source is not None else None,
+                                         RESAMPLE_CLAMP if clamp else 0, C.byref(outside),
+                                         C.byref(clamped)))
+        return outside.value, clamped.value
 
     def elevation_scalar(self, x, y, want_inside=True):
         z, inside = C.c_double(-12345.0), C.c_int(-1)

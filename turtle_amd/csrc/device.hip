@@ -504,11 +504,15 @@ __constant__ double kLambert[6][6] = {
         { 0.08181919112, 0.7253743710, 11755528.70, 0.05235987756, 700000.0, 12657560.145 }
 };
 
-/* [ref projection.c:192-210, :238-244, :286-295 (Lambert), :377-408 (UTM)] */
-__device__ __noinline__ void d_project(
+/* [ref projection.c:192-210, :238-244, :286-295 (Lambert), :377-408 (UTM)].  The kernels
+ * call d_project / d_unproject, out of line; k_resample, whose whole work they are, has the
+ * bodies inlined (a call takes its outputs through scratch memory). */
+/* TYPE: TAMD_PROJ_LAMBERT or _UTM when the caller knows it, else -2: decided by pr.type */
+template <int TYPE = -2>
+__device__ __forceinline__ void d_project_body(
     const tamd_proj & pr, double latitude, double longitude, double & x, double & y)
 {
-        if (pr.type == TAMD_PROJ_LAMBERT) {
+        if ((TYPE == TAMD_PROJ_LAMBERT) || ((TYPE != TAMD_PROJ_UTM) && (pr.type == TAMD_PROJ_LAMBERT))) {
                 const double * P = kLambert[pr.lambert_tag];
                 const double e = P[0];
                 const double phi = latitude * kPi / 180.;
@@ -546,11 +550,18 @@ __device__ __noinline__ void d_project(
         y = N0 + k0 * A * (zeta + ys);
 }
 
+__device__ __noinline__ void d_project(
+    const tamd_proj & pr, double latitude, double longitude, double & x, double & y)
+{
+        d_project_body(pr, latitude, longitude, x, y);
+}
+
 /* [ref projection.c:213-230, :253-268, :304-318 (Lambert), :417-448 (UTM)] */
-__device__ __noinline__ void d_unproject(
+template <int TYPE = -2>
+__device__ __forceinline__ void d_unproject_body(
     const tamd_proj & pr, double x, double y, double & latitude, double & longitude)
 {
-        if (pr.type == TAMD_PROJ_LAMBERT) {
+        if ((TYPE == TAMD_PROJ_LAMBERT) || ((TYPE != TAMD_PROJ_UTM) && (pr.type == TAMD_PROJ_LAMBERT))) {
                 const double * P = kLambert[pr.lambert_tag];
                 const double e = P[0];
                 const double dx = x - P[4];
@@ -595,6 +606,12 @@ __device__ __noinline__ void d_unproject(
         for (int i = 0; i < 3; i++) s += delta[i] * sin(2. * (i + 1) * chi);
         latitude = (chi + s) * 180. / kPi;
         longitude = pr.longitude_0 + atan2(sinh(eta), cos(zeta)) * 180. / kPi;
+}
+
+__device__ __noinline__ void d_unproject(
+    const tamd_proj & pr, double x, double y, double & latitude, double & longitude)
+{
+        d_unproject_body(pr, x, y, latitude, longitude);
 }
 
 /* ---- one grid --------------------------------------------------------- */
@@ -3591,6 +3608,151 @@ __global__ void __launch_bounds__(256) k_tally(long n, const int * __restrict__ 
         }
 }
 
+/* ---- turtle_map_resample ------------------------------------------------------
+ * Every node of a target map filled from a stack or another map: the loop of the
+ * reference's examples/example-projection.c (turtle_map_node, _unproject,
+ * turtle_stack_elevation, turtle_map_fill) in one launch.  One WAVE per 8 x 8 block of
+ * the target, its 64 lanes the block's 64 nodes in the HBM order (internal.h): the
+ * wave's store of the new codes is one 128-byte line, and neighbouring lanes look up
+ * neighbouring source cells.  The kernel writes a whole new copy of the target in that
+ * layout; a node that stays as it is (outside the data, or outside the map's span
+ * without TURTLE_AMD_RESAMPLE_CLAMP) gets the code of the map's current copy, so that a
+ * block's work can be done again and the copy is complete whatever the host decides.
+ * Lookups are the strict bilinear ones of k_elevation: the result does not depend on
+ * the arithmetic mode. */
+enum { RS_STACK = 0, RS_MAP = 1 };
+
+/* page_fault for an item that is a whole wave (a target block): the block is listed
+ * once if any of its nodes met a tile that is not resident, and is redone whole in a
+ * later round; each tile it wants counts once per block (the usual case: one tile), a
+ * seam's neighbours once per node that wants them */
+__device__ __forceinline__ void page_fault_block(const Paging & pg, const TileFault & f, int item)
+{
+        const bool fault = f.centre >= 0;
+        const ull mask = __ballot(fault);
+        if (mask == 0) return;
+        const int lane = (int)(threadIdx.x & 63);
+        const int leader = __builtin_ctzll(mask);
+        ull base = 0;
+        if (lane == leader) {
+                base = atomicAdd(pg.n_faulted, 1ull);
+                pg.faulted[base] = item;
+        }
+        base = __shfl(base, leader, 64);
+        const bool first = (pg.first_id >= 0) ? (item == pg.first_id) : (base == 0);
+        if (fault) {
+                for (int b = 0; b < 9; b++) {
+                        if (!((f.mask >> b) & 1)) continue;
+                        const int t = f.centre + (b / 3 - 1) * f.stride + (b % 3 - 1);
+                        if (b != 4) atomicAdd(&pg.wanted[(size_t)t * TAMD_DEMAND_STRIDE], 1u);
+                        if (first) atomicOr(&pg.wanted_first[t >> 5], 1u << (t & 31));
+                }
+        }
+        const bool centre = fault && (((f.mask >> 4) & 1) != 0);
+        ull left = __ballot(centre);
+        while (left != 0) {
+                const int lead = __builtin_ctzll(left);
+                const int t0 = __shfl(f.centre, lead, 64);
+                const ull same = __ballot(centre && (f.centre == t0));
+                if (lane == lead) atomicAdd(&pg.wanted[(size_t)t0 * TAMD_DEMAND_STRIDE], 1u);
+                left &= ~same;
+        }
+}
+
+/* grids[0]: the target (nodes: its current HBM copy; x0 .. dy, nbx and proj as the
+ * map holds them); grids[1]: the source map (RS_MAP).  z0, dz, is_signed: the
+ * target's own encoding, as turtle_map_fill applies it.  counters (zeroed by the
+ * caller, added to round after round): nodes outside the data, nodes outside the span
+ * and not clamped, nodes clamped.  Items are the target's blocks; over a paged stack,
+ * a block with a faulting node is listed and none of its work is kept. */
+template <int SRC, int TPROJ /* the target's projection type */>
+__global__ void __launch_bounds__(256) k_resample(tamd_view v, const tamd_grid * __restrict__ grids,
+    double z0, double dz, int is_signed, int flags, long n_blocks, uint16_t * __restrict__ out, Paging pg,
+    ull * __restrict__ counters)
+{
+        const tamd_grid & t = grids[0];
+        const int lane = (int)(threadIdx.x & 63);
+        const long waves = (long)gridDim.x * (blockDim.x >> 6);
+        const long n_items = (pg.n_in != nullptr) ? (long)*pg.n_in : n_blocks;
+        const double top = z0 + 65535 * dz; /* [ref map.c:196-197] */
+        ull n_outside = 0, n_bad = 0, n_clamped = 0;
+        for (long i = blockIdx.x * (long)(blockDim.x >> 6) + (threadIdx.x >> 6); i < n_items; i += waves) {
+                const long blk = (pg.ids != nullptr) ? (long)pg.ids[i] : i;
+                const int ix = (int)(blk % t.nbx) * TAMD_BLOCK + (lane & 7);
+                const int iy = (int)(blk / t.nbx) * TAMD_BLOCK + (lane >> 3);
+                TileFault f = { -1, 0, 0 };
+                bool keep = true;
+                int outside = 0, bad = 0, clamped = 0;
+                uint16_t code = 0;
+                if ((ix < t.nx) && (iy < t.ny)) {
+                        /* turtle_map_node [ref map.c:217-218] */
+                        const double x = t.x0 + ix * t.dx;
+                        const double y = t.y0 + iy * t.dy;
+                        double latitude, longitude;
+                        if (TPROJ >= 0)
+                                d_unproject_body<TPROJ>(t.proj, x, y, latitude, longitude);
+                        else
+                                latitude = y, longitude = x;
+                        double z = 0.;
+                        int in;
+                        if (SRC == RS_STACK) {
+                                in = d_stack_elevation<false>(v, v.stacks[0], latitude, longitude, z, f);
+                                if (in >= 0) f.centre = -1;
+                        } else {
+                                const tamd_grid & s = grids[1];
+                                double u, w;
+                                if (flags & TAMD_RESAMPLE_IDENTITY)
+                                        u = x, w = y;
+                                else if (s.proj.type >= 0)
+                                        d_project_body(s.proj, latitude, longitude, u, w);
+                                else
+                                        u = longitude, w = latitude;
+                                in = d_grid_elevation<false>(s, u, w, z) ? 1 : 0;
+                        }
+                        if (in == 0) {
+                                outside = 1;
+                        } else if (in > 0) {
+                                /* turtle_map_fill [ref map.c:192-200, :47-51] */
+                                const bool off = ((dz <= 0.) && (z != z0)) || (z < z0) || (z > top);
+                                if (off && !(flags & TURTLE_AMD_RESAMPLE_CLAMP)) {
+                                        bad = 1;
+                                } else {
+                                        if (off) {
+                                                clamped = 1;
+                                                z = ((dz <= 0.) || (z < z0)) ? z0 : top;
+                                        }
+                                        if (is_signed)
+                                                code = (uint16_t)(int)z; /* (int16)z */
+                                        else
+                                                code = (dz > 0.) ? (uint16_t)(unsigned)round((z - z0) / dz) : 0;
+                                        keep = false;
+                                }
+                        }
+                }
+                if (pg.faulted != nullptr) {
+                        const bool redo = __ballot(f.centre >= 0) != 0;
+                        page_fault_block(pg, f, (int)blk);
+                        if (redo) continue; /* (the whole wave) */
+                }
+                const size_t k = (size_t)blk * 64 + lane;
+                if (keep) code = GLOBAL_NODES(t.nodes)[k];
+                out[k] = code;
+                n_outside += outside, n_bad += bad, n_clamped += clamped;
+        }
+        block_tally(counters, n_outside, n_bad, n_clamped, 0);
+}
+
+/* The host copy of a map from its HBM copy: rows of nx nodes, south to north */
+__global__ void k_unblock(const uint16_t * __restrict__ blocked, int nx, int ny, int nbx,
+    uint16_t * __restrict__ rows)
+{
+        const long n = (long)nx * ny;
+        for (long k = blockIdx.x * (long)blockDim.x + threadIdx.x; k < n; k += (long)gridDim.x * blockDim.x) {
+                const int iy = (int)(k / nx), ix = (int)(k - (long)iy * nx);
+                rows[k] = GLOBAL_NODES(blocked)[d_node_index(nbx, ix, iy)];
+        }
+}
+
 } /* namespace */
 
 /* ======================================================================== */
@@ -4659,5 +4821,45 @@ extern "C" int tamd_k_tally(long n, const int * index, const double * length,
         hipLaunchKernelGGL(k_tally, dim3(grid_for(n, 256)), dim3(256), lds, g_stream, n,
             index, length, n_media, hits, n_bins, scale, histogram);
         LAUNCH_CHECK("k_tally");
+        return 0;
+}
+
+extern "C" int tamd_k_resample(struct tamd_view view, const struct tamd_grid * grids, int from_map,
+    double z0, double dz, int is_signed, int flags, long n_blocks, uint16_t * out,
+    struct tamd_paging pg, unsigned long long * counters)
+{
+        if (tamd_dev_init()) return 1;
+        if (n_blocks <= 0) return 0;
+        /* the target's projection: a host field, read back from its table */
+        struct tamd_grid target;
+        if (tamd_dev_d2h(&target, grids, sizeof(target))) return 1;
+        const dim3 blocks(grid_for(n_blocks * 64, 256));
+#define RS_LAUNCH(S, P)                                                                            \
+        hipLaunchKernelGGL((k_resample<S, P>), blocks, dim3(256), 0, g_stream, view, grids, z0, dz,      \
+            is_signed, flags, n_blocks, out, pg, counters)
+#define RS_LAUNCH_ALL(S)                                                                           \
+        do {                                                                                       \
+                if (target.proj.type == TAMD_PROJ_LAMBERT) RS_LAUNCH(S, TAMD_PROJ_LAMBERT);        \
+                else if (target.proj.type == TAMD_PROJ_UTM) RS_LAUNCH(S, TAMD_PROJ_UTM);           \
+                else RS_LAUNCH(S, TAMD_PROJ_NONE);                                                 \
+        } while (0)
+        if (from_map)
+                RS_LAUNCH_ALL(RS_MAP);
+        else
+                RS_LAUNCH_ALL(RS_STACK);
+#undef RS_LAUNCH_ALL
+#undef RS_LAUNCH
+        LAUNCH_CHECK("k_resample");
+        return 0;
+}
+
+extern "C" int tamd_k_unblock(const uint16_t * blocked, int nx, int ny, int nbx, uint16_t * rows)
+{
+        if (tamd_dev_init()) return 1;
+        const long n = (long)nx * ny;
+        if (n <= 0) return 0;
+        hipLaunchKernelGGL(k_unblock, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, blocked, nx, ny,
+            nbx, rows);
+        LAUNCH_CHECK("k_unblock");
         return 0;
 }

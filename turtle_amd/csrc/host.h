@@ -204,6 +204,10 @@ extern unsigned long tamd_stack_buffer_hits;
 #define TAMD_PAGING_SLACK 8
 int tamd_stack_page_in(struct turtle_stack * stack, const unsigned * wanted,
     const unsigned * wanted_first, int first_bit, int few, char * message, size_t size);
+/* The one-stack view of the elevation kernels (metas[0]: the stack), in a device block of the
+ * calling thread; 0, -1 on a device error, or a positive enum turtle_return with `message` set.
+ * Hold the geometry in use from here until the launches that read it are queued. */
+int tamd_stack_view(struct turtle_stack * stack, struct tamd_view * view, char * message, size_t size);
 
 struct turtle_client {
         struct turtle_stack * stack;

@@ -283,6 +283,20 @@ int tamd_k_project(struct tamd_proj proj, int inverse, long n, const double * a,
 int tamd_k_tally(long n, const int * index, const double * length,
     int n_media, unsigned long long * hits, int n_bins, double length_max,
     unsigned long long * histogram);
+/* turtle_map_resample: every block of the target grids[0] (a device table; its nodes are the
+ * map's current HBM copy) from metas[0] of the view, a STACK (from_map == 0), or from the map
+ * grids[1].  out: a whole new copy of the target in the HBM layout (n_blocks x 64 nodes); z0, dz,
+ * is_signed: the target's encoding as turtle_map_fill applies it; flags: enum
+ * turtle_amd_resample_flags | TAMD_RESAMPLE_IDENTITY (the source map has the target's
+ * projection: it is looked up at the node's own x, y).  counters: 4 x uint64, zeroed by the
+ * caller and added to round after round -- nodes outside the data, nodes outside the span and
+ * not clamped, nodes clamped.  Over a paged stack the items of `pg` are blocks. */
+#define TAMD_RESAMPLE_IDENTITY 0x100
+int tamd_k_resample(struct tamd_view view, const struct tamd_grid * grids, int from_map,
+    double z0, double dz, int is_signed, int flags, long n_blocks, uint16_t * out,
+    struct tamd_paging pg, unsigned long long * counters);
+/* the map's host rows (south to north) from an HBM copy */
+int tamd_k_unblock(const uint16_t * blocked, int nx, int ny, int nbx, uint16_t * rows);
 
 #ifdef __cplusplus
 }

@@ -700,6 +700,11 @@ static int stack_view(struct turtle_stack * s, struct tamd_view * view, char * m
         return 0;
 }
 
+int tamd_stack_view(struct turtle_stack * stack, struct tamd_view * view, char * message, size_t size)
+{
+        return stack_view(stack, view, message, size);
+}
+
 /* The rounds of a batch call on one stack (paging.c): `launch` runs the kernel
  * of a round.  Returns 0, -1 (device) or a positive enum turtle_return. */
 struct stack_call {
