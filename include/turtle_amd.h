@@ -568,7 +568,41 @@ TURTLE_API enum turtle_return turtle_stepper_traverse_n(
     int * index /* [n][2], out: final */, double * length /* [media][n] or NULL */,
     int * n_steps /* [n] or NULL */, int * n_crossings /* [n] or NULL */, int space);
 
-/* Totals of the LAST trace_n, scatter_n or traverse_n call on this stepper,
+/* Lines of sight with every crossing point: turtle_stepper_traverse_n's loop and outputs, and
+ * where each ray changed medium.  For each ray r, exactly (a fresh stepper history per ray):
+ *
+ *     turtle_stepper_step(s, pos, NULL, NULL, NULL, &alt, NULL, NULL, idx);  d = 0;
+ *     while (idx[0] >= 0 && alt < altitude_max && steps < max_steps) {
+ *             m = idx[0];  turtle_stepper_step(s, pos, dir, NULL, NULL, &alt, NULL, &ds, idx);
+ *             length[m*n + r] += ds;  d += ds;  steps++;
+ *             if (idx[0] != m) {
+ *                     c = crossings++;
+ *                     if (c < capacity) { point[c][r] = pos; distance[c][r] = d; media[c][r] = {m, idx[0]}; }
+ *             }
+ *     }
+ *
+ * n_crossings[r] is the true count: it may exceed capacity, and then only the first `capacity`
+ * crossings are recorded.  The slots from min(n_crossings[r], capacity) on are zero: point and
+ * distance 0, media {0, 0} (no crossing has that pair).  Leaving the data is a crossing, media
+ * {m, -1}, at the ray's final position; stopping at the ceiling or at max_steps is not.  The
+ * slot arrays are crossing-major, as length is medium-major: slot c of ray r is element
+ * (long)c * n + r, each slot's column contiguous.  point, distance, media, length and n_steps may
+ * be NULL; capacity = 0 records nothing (traverse_n with the counts).  position, index, length,
+ * n_steps and n_crossings are bit for bit those of turtle_stepper_traverse_n on the same inputs,
+ * in either arithmetic, resident or paged: recording a crossing changes no decision and no
+ * addition.  turtle_stepper_trace_stats reports the call as it does traverse_n.  BAD_ADDRESS:
+ * position, direction, index or n_crossings NULL; DOMAIN_ERROR: max_steps < 0 or capacity < 0;
+ * n <= 0 does nothing. */
+TURTLE_API enum turtle_return turtle_stepper_crossings_n(
+    struct turtle_stepper * stepper, long n, double * position /* [n][3], in / out */,
+    const double * direction /* [n][3] */, double altitude_max, int max_steps,
+    int * index /* [n][2], out: final */, double * length /* [media][n] or NULL */,
+    int * n_steps /* [n] or NULL */, int * n_crossings /* [n], mandatory */,
+    int capacity, double * point /* [capacity][n][3] or NULL */,
+    double * distance /* [capacity][n] or NULL */, int * media /* [capacity][n][2] or NULL */,
+    int space);
+
+/* Totals of the LAST trace_n, scatter_n, traverse_n or crossings_n call on this stepper,
  * accumulated on the device: stats[0] rays, [1] steps, [2] samples (transform +
  * layer lookup; the same from run to run), [3] rays that stopped at max_steps.
  * Synchronises the stream. */

@@ -635,6 +635,32 @@ class Stepper:
         return dict(position=pos, index=index, length=length, n_steps=nsteps,
                     n_crossings=ncross)
 
+    def crossings(self, position, direction, altitude_max=float("inf"), max_steps=1000000,
+                  capacity=32, want=("length", "n_steps", "point", "distance", "media")):
+        """turtle_stepper_crossings_n: traverse's loop and outputs (n_crossings always), plus the
+        first `capacity` crossings of each ray, crossing-major: `point` (capacity, n, 3) where the
+        ray crossed, `distance` (capacity, n) its path from the origin to there, `media`
+        (capacity, n, 2) the pair {medium left, medium entered} (entered -1: it left the data).
+        Slots past a ray's n_crossings are zero."""
+        sp = _space_of(position, direction)
+        pos = _as(position, sp).reshape(-1, 3)
+        d = _as(direction, sp).reshape(-1, 3)
+        n = pos.shape[0]
+        index = _new((n, 2), sp, np.int32, like=pos)
+        length = _new((self.media, n), sp, like=pos) if "length" in want else None
+        nsteps = _new((n,), sp, np.int32, like=pos) if "n_steps" in want else None
+        ncross = _new((n,), sp, np.int32, like=pos)
+        point = _new((capacity, n, 3), sp, like=pos) if "point" in want else None
+        distance = _new((capacity, n), sp, like=pos) if "distance" in want else None
+        media = _new((capacity, n, 2), sp, np.int32, like=pos) if "media" in want else None
+        _check(lib().turtle_stepper_crossings_n(self.h, C.c_long(n), _ptr(pos), _ptr(d),
+                                                C.c_double(altitude_max), int(max_steps),
+                                                _ptr(index), _ptr(length), _ptr(nsteps),
+                                                _ptr(ncross), int(capacity), _ptr(point),
+                                                _ptr(distance), _ptr(media), sp))
+        return dict(position=pos, index=index, length=length, n_steps=nsteps,
+                    n_crossings=ncross, point=point, distance=distance, media=media)
+
     def trace_into(self, pos, d, index, length, nsteps, max_steps=100000):
         """Device-resident trace with caller-owned tensors (no allocation):
         the timed call of bench.py."""

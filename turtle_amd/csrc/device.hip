@@ -3386,9 +3386,19 @@ struct TraverseIO {
         int max_steps;
 };
 
-template <int MODE, bool FAST>
+/* REC (turtle_stepper_crossings_n): one more register, the ray's total path `tot`, summed as len
+ * is (an accepted step's ds, a located crossing's ds + ds1), and each located crossing stored into
+ * slot `crossings` of the [capacity][n] arrays (the new position, tot, {m, bm}) before the count
+ * goes up.  Nothing else changes: the same decisions and additions, the same bits as REC = false,
+ * whose instances take an empty last argument. */
+struct NoCrossings {};
+template <bool REC> struct CrossingsArg { typedef NoCrossings type; };
+template <> struct CrossingsArg<true> { typedef tamd_crossings type; };
+
+template <int MODE, bool FAST, bool REC>
 __global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * __restrict__ pos,
-    int * __restrict__ index, TraverseIO io, ull * __restrict__ stats, ull * __restrict__ queue)
+    int * __restrict__ index, TraverseIO io, ull * __restrict__ stats, ull * __restrict__ queue,
+    typename CrossingsArg<REC>::type rec)
 {
         long pool_next = 0, pool_end = 0; /* wave-uniform */
         bool exhausted = false;            /* wave-uniform */
@@ -3401,6 +3411,7 @@ __global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * 
         bool dead = false;
         int state = ST_INIT, count = 0, crossings = 0;
         double bx = 0, by = 0, bz = 0, dx = 0, dy = 0, dz = 0, len = 0;
+        double tot = 0; /* (REC) the path since the origin */
         double ds = 0, ds0 = 0, ds1 = 0;
         double s_alt = 0, s_e0 = 0, s_e1 = 0; /* the sample the ray stands on */
         double b_alt = 0, b_e0 = 0, b_e1 = 0; /* the bisection's last sample of the new medium */
@@ -3437,6 +3448,7 @@ __global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * 
                                 bx = pos[3 * ray], by = pos[3 * ray + 1], bz = pos[3 * ray + 2];
                                 dx = io.dir[3 * ray], dy = io.dir[3 * ray + 1], dz = io.dir[3 * ray + 2];
                                 state = ST_INIT, count = 0, crossings = 0, len = 0.;
+                                if constexpr (REC) tot = 0.;
                         }
                         pool_next += min((long)__popcll(mask), avail);
                 }
@@ -3477,10 +3489,23 @@ __global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * 
                                 if (accept) {
                                         len += ds, k = s.k;
                                         s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
+                                        if constexpr (REC) tot += ds;
                                 }
                                 if (located) { /* [ref stepper.c:861-863] */
                                         bx = bx + dx * ds1, by = by + dy * ds1, bz = bz + dz * ds1;
                                         len += ds + ds1;
+                                        if constexpr (REC) {
+                                                tot += ds + ds1;
+                                                if (crossings < rec.capacity) { /* slot [crossings][ray] */
+                                                        const long c = (long)crossings * n + ray;
+                                                        if (rec.point != nullptr)
+                                                                rec.point[3 * c] = bx, rec.point[3 * c + 1] = by,
+                                                                rec.point[3 * c + 2] = bz;
+                                                        if (rec.distance != nullptr) rec.distance[c] = tot;
+                                                        if (rec.media != nullptr)
+                                                                rec.media[2 * c] = m, rec.media[2 * c + 1] = bm;
+                                                }
+                                        }
                                         /* the sum of the medium left goes out, the new one's comes in */
                                         if (io.length != nullptr) {
                                                 io.length[(long)m * n + ray] = len;
@@ -3552,6 +3577,32 @@ __global__ void k_traverse_gen(long n, int first, const double * __restrict__ al
                 }
         }
         block_tally(counters, my_rays, my_steps, my_capped, my_live);
+}
+
+/* A paged turtle_stepper_crossings_n, after a generation's steps and before its k_traverse_gen
+ * (which still holds the medium each live ray started in, and its crossing count): the step added
+ * to the ray's running total, and a ray whose medium changed (m1 != m0) records its new position,
+ * that total and {m0, m1} in slot n_cross[r].  k_traverse<REC>'s additions: the same bits. */
+__global__ void k_crossings_gen(long n, const double * __restrict__ pos, const double * __restrict__ step,
+    const int * __restrict__ live_index, const int * __restrict__ medium, const int * __restrict__ n_cross,
+    double * __restrict__ total, tamd_crossings rec)
+{
+        for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
+             r += (long)gridDim.x * blockDim.x) {
+                const int m0 = medium[r];
+                if (m0 < 0) continue; /* done earlier */
+                const double tot = total[r] + step[r];
+                total[r] = tot;
+                const int m1 = live_index[2 * r];
+                if ((m1 != m0) && (n_cross[r] < rec.capacity)) {
+                        const long c = (long)n_cross[r] * n + r;
+                        if (rec.point != nullptr)
+                                rec.point[3 * c] = pos[3 * r], rec.point[3 * c + 1] = pos[3 * r + 1],
+                                rec.point[3 * c + 2] = pos[3 * r + 2];
+                        if (rec.distance != nullptr) rec.distance[c] = tot;
+                        if (rec.media != nullptr) rec.media[2 * c] = m0, rec.media[2 * c + 1] = m1;
+                }
+        }
 }
 
 __global__ void k_philox(long n, ull seed, ull stream, long first, unsigned * __restrict__ out)
@@ -4720,10 +4771,27 @@ extern "C" int tamd_k_walk(struct tamd_view view, long n, double * pos, double *
         return 0;
 }
 
+template <int MODE, bool REC>
+static void launch_traverse(const tamd_view & view, long n, double * pos, int * index, const TraverseIO & io,
+    ull * stats, ull * queue, bool strict, typename CrossingsArg<REC>::type rec)
+{
+        const void * kernel = strict ? (const void *)k_traverse<MODE, false, REC> :
+                                       (const void *)k_traverse<MODE, true, REC>;
+        long blocks = (long)g_cus * trace_blocks_per_cu(kernel);
+        const long useful = (n + 255) / 256;
+        if (blocks > useful) blocks = useful;
+        if (strict)
+                hipLaunchKernelGGL((k_traverse<MODE, false, REC>), dim3((unsigned)blocks), dim3(256), 0,
+                    g_stream, view, n, pos, index, io, stats, queue, rec);
+        else
+                hipLaunchKernelGGL((k_traverse<MODE, true, REC>), dim3((unsigned)blocks), dim3(256), 0,
+                    g_stream, view, n, pos, index, io, stats, queue, rec);
+}
+
 /* A whole traverse in one launch (k_traverse): every tile resident, nothing listed */
 extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, const double * dir,
     double ceiling, int max_steps, int * index, double * length, int * n_steps, int * n_cross,
-    unsigned long long * stats, unsigned long long * queue)
+    const struct tamd_crossings * rec, unsigned long long * stats, unsigned long long * queue)
 {
         if (tamd_dev_init()) return 1;
         HIP_TRY(hipMemsetAsync(stats, 0, 4 * sizeof(ull), g_stream));
@@ -4733,17 +4801,11 @@ extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, cons
         const bool strict = g_math_strict || !view.fast_ok;
 #define TRAVERSE_CASE(MODE)                                                                    \
         do {                                                                                   \
-                const void * kernel = strict ? (const void *)k_traverse<MODE, false> :        \
-                                               (const void *)k_traverse<MODE, true>;           \
-                long blocks = (long)g_cus * trace_blocks_per_cu(kernel);                       \
-                const long useful = (n + 255) / 256;                                           \
-                if (blocks > useful) blocks = useful;                                          \
-                if (strict)                                                                    \
-                        hipLaunchKernelGGL((k_traverse<MODE, false>), dim3((unsigned)blocks), dim3(256), 0, \
-                            g_stream, view, n, pos, index, io, stats, queue);                  \
+                if (rec != nullptr)                                                            \
+                        launch_traverse<MODE, true>(view, n, pos, index, io, stats, queue, strict, *rec); \
                 else                                                                           \
-                        hipLaunchKernelGGL((k_traverse<MODE, true>), dim3((unsigned)blocks), dim3(256), 0,  \
-                            g_stream, view, n, pos, index, io, stats, queue);                  \
+                        launch_traverse<MODE, false>(view, n, pos, index, io, stats, queue, strict, \
+                            NoCrossings());                                                    \
         } while (0)
         if (view.mode == TAMD_MODE_ONE_MAP)
                 TRAVERSE_CASE(TAMD_MODE_ONE_MAP);
@@ -4781,6 +4843,17 @@ extern "C" int tamd_k_traverse_gen(long n, int first, const double * alt, const 
             alt, step, live_index, medium, index, length, n_steps, n_cross, ceiling, max_steps,
             counters);
         LAUNCH_CHECK("k_traverse_gen");
+        return 0;
+}
+
+extern "C" int tamd_k_crossings_gen(long n, const double * pos, const double * step, const int * live_index,
+    const int * medium, const int * n_cross, double * total, struct tamd_crossings rec)
+{
+        if (tamd_dev_init()) return 1;
+        if (n <= 0) return 0;
+        hipLaunchKernelGGL(k_crossings_gen, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, n, pos, step,
+            live_index, medium, n_cross, total, rec);
+        LAUNCH_CHECK("k_crossings_gen");
         return 0;
 }
 

@@ -254,14 +254,23 @@ int tamd_k_walk(struct tamd_view view, long n, double * pos, double * alt, doubl
 /* a flag of the step kernels: a ray whose index[r][0] is -1 takes no step and is left as it is (the
  * rays a paged turtle_stepper_traverse_n has finished) */
 #define TAMD_STEP_LIVE 0x400
+/* where turtle_stepper_crossings_n records crossing c of ray r: element c * n + r of each array
+ * (zeroed by the caller), for c < capacity */
+struct tamd_crossings {
+        double * point;    /* [capacity][n][3] or NULL */
+        double * distance; /* [capacity][n] or NULL */
+        int * media;       /* [capacity][n][2] or NULL */
+        int capacity;
+};
 /* turtle_stepper_traverse_n, every tile resident: each ray sampled at its origin, then stepped
  * along dir until it leaves the data, reaches `ceiling` or has taken max_steps steps, its path
  * length summed per medium into length[m * n + r] (zeroed by the caller; or NULL); n_steps and
- * n_cross may be NULL.  stats (rays, steps, samples, rays stopped by max_steps) and queue[0] are
- * zeroed by the launcher. */
+ * n_cross may be NULL.  rec: where to record the crossings (turtle_stepper_crossings_n), or NULL.
+ * stats (rays, steps, samples, rays stopped by max_steps) and queue[0] are zeroed by the
+ * launcher. */
 int tamd_k_traverse(struct tamd_view view, long n, double * pos, const double * dir,
     double ceiling, int max_steps, int * index, double * length, int * n_steps, int * n_cross,
-    unsigned long long * stats, unsigned long long * queue);
+    const struct tamd_crossings * rec, unsigned long long * stats, unsigned long long * queue);
 /* the generation-by-generation form over paged stacks: one step of every ray whose index[r][0]
  * >= 0, resumed from alt / elev / index (tamd_k_step_dir with TURTLE_AMD_STEP_RESUME |
  * TAMD_STEP_LIVE; stats NOT zeroed); then tamd_k_traverse_gen adds what it took to the sums.
@@ -273,6 +282,11 @@ int tamd_k_step_live(struct tamd_view view, long n, double * pos, const double *
 int tamd_k_traverse_gen(long n, int first, const double * alt, const double * step, int * live_index,
     int * medium, int * index, double * length, int * n_steps, int * n_cross, double ceiling,
     int max_steps, unsigned long long * counters);
+/* the crossings of a paged turtle_stepper_crossings_n, launched after each generation's steps and
+ * before its tamd_k_traverse_gen: each live ray's step added to its running total (zeroed by the
+ * caller), and a ray whose medium changed recorded into slot n_cross[r] */
+int tamd_k_crossings_gen(long n, const double * pos, const double * step, const int * live_index,
+    const int * medium, const int * n_cross, double * total, struct tamd_crossings rec);
 int tamd_k_philox(long n, unsigned long long seed, unsigned long long stream,
     long first, unsigned * out);
 int tamd_k_isotropic(long n, unsigned long long seed, unsigned long long stream,

@@ -994,11 +994,12 @@ static void * traverse_piece(char * block, size_t * used, size_t bytes)
  * same values as k_traverse in STRICT: the same bits. */
 static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos, const double * dir,
     double ceiling, int max_steps, int * index, double * length, int * n_steps, int * n_cross,
-    char * message, size_t size)
+    const struct tamd_crossings * rec, char * message, size_t size)
 {
-        /* the sample state between generations, and the counts the caller may not want */
+        /* the sample state between generations, the counts the caller may not want and, recording
+         * crossings, the running totals */
         const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int);
-        const size_t bytes = 4 * nb + 5 * ni + 4 * sizeof(unsigned long long) + 7 * 256;
+        const size_t bytes = (4 + (rec != NULL)) * nb + 5 * ni + 4 * sizeof(unsigned long long) + 8 * 256;
         char * block;
         if (tamd_dev_malloc((void **)&block, bytes)) return TURTLE_RETURN_LIBRARY_ERROR;
         size_t used = 0;
@@ -1010,6 +1011,7 @@ static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos,
         int * medium = traverse_piece(block, &used, ni);
         int * own = traverse_piece(block, &used, 2 * ni);
         unsigned long long * counters = traverse_piece(block, &used, 4 * sizeof(unsigned long long));
+        double * total = (rec != NULL) ? traverse_piece(block, &used, nb) : NULL;
         if (n_steps == NULL) n_steps = own;
         if (n_cross == NULL) n_cross = own + n;
         /* counters: [0, 4) k_traverse_gen's; the step kernels' stats are in d_stats[8, 12) */
@@ -1017,6 +1019,7 @@ static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos,
         int rounds = stepper->last_rounds; /* (turtle_amd_stepper_rounds: the most a generation took) */
         if ((rc == 0) && (tamd_dev_zero(counters, 4 * sizeof(*counters)) ||
                              tamd_dev_zero(stepper->d_stats + 8, 4 * sizeof(*stepper->d_stats)) ||
+                             ((total != NULL) && tamd_dev_zero(total, nb)) ||
                              tamd_k_traverse_gen(n, 1, a.alt, NULL, a.live, medium, index, length,
                                  n_steps, n_cross, ceiling, max_steps, counters)))
                 rc = TURTLE_RETURN_LIBRARY_ERROR;
@@ -1033,6 +1036,9 @@ static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos,
                 }
                 rc = stepper_rounds(stepper, n, &traverse_round, &a, message, size);
                 if (stepper->last_rounds > rounds) rounds = stepper->last_rounds;
+                if ((rc == 0) && (total != NULL) &&
+                    tamd_k_crossings_gen(n, a.pos, a.step, a.live, medium, n_cross, total, *rec))
+                        rc = TURTLE_RETURN_LIBRARY_ERROR;
                 if ((rc == 0) && tamd_k_traverse_gen(n, 0, a.alt, a.step, a.live, medium, index, length,
                                      n_steps, n_cross, ceiling, max_steps, counters))
                         rc = TURTLE_RETURN_LIBRARY_ERROR;
@@ -1051,11 +1057,12 @@ static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos,
         return rc;
 }
 
-enum turtle_return turtle_stepper_traverse_n(struct turtle_stepper * stepper, long n,
+/* turtle_stepper_traverse_n and, rec != NULL (the caller's arrays), turtle_stepper_crossings_n */
+static enum turtle_return traverse_n(struct tamd_error * error, struct turtle_stepper * stepper, long n,
     double * position, const double * direction, double altitude_max, int max_steps, int * index,
-    double * length, int * n_steps, int * n_crossings, int space)
+    double * length, int * n_steps, int * n_crossings, const struct tamd_crossings * rec, int space)
 {
-        TAMD_ERROR_INIT(&turtle_stepper_traverse_n);
+        struct tamd_error error_ = *error;
         if ((position == NULL) || (direction == NULL) || (index == NULL))
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
         if (max_steps < 0) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid input parameter(s)");
@@ -1071,34 +1078,71 @@ enum turtle_return turtle_stepper_traverse_n(struct turtle_stepper * stepper, lo
         }
         const long media = stepper->n_layers + 1;
         struct tamd_stage st;
-        void *dp, *dd, *dix, *dlen, *dst, *dcr;
+        void *dp, *dd, *dix, *dlen, *dst, *dcr, *dpt = NULL, *ddi = NULL, *dme = NULL;
         const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int);
-        if (tamd_stage_begin(&st, space, (6 + media) * nb + 4 * ni) ||
+        const size_t slots = (rec != NULL) ? (size_t)rec->capacity : 0; /* (of n rays each) */
+        if (tamd_stage_begin(&st, space, (6 + media + 4 * slots) * nb + (4 + 2 * slots) * ni) ||
             tamd_stage_in(&st, position, 3 * nb, &dp) || tamd_stage_in(&st, direction, 3 * nb, &dd) ||
             tamd_stage_out(&st, index, 2 * ni, &dix) || tamd_stage_out(&st, length, media * nb, &dlen) ||
-            tamd_stage_out(&st, n_steps, ni, &dst) || tamd_stage_out(&st, n_crossings, ni, &dcr))
+            tamd_stage_out(&st, n_steps, ni, &dst) || tamd_stage_out(&st, n_crossings, ni, &dcr) ||
+            ((rec != NULL) && (tamd_stage_out(&st, rec->point, 3 * slots * nb, &dpt) ||
+                                  tamd_stage_out(&st, rec->distance, slots * nb, &ddi) ||
+                                  tamd_stage_out(&st, rec->media, 2 * slots * ni, &dme))))
                 return TAMD_RAISE_DEVICE();
-        /* the sums are added to where they stand: they start from zero */
+        /* the sums are added to where they stand: they start from zero; and the slots past a ray's
+         * crossings are zero (media {0, 0}) */
         if ((dlen != NULL) && tamd_dev_zero(dlen, media * nb)) return TAMD_RAISE_DEVICE();
+        if ((slots > 0) && (((dpt != NULL) && tamd_dev_zero(dpt, 3 * slots * nb)) ||
+                               ((ddi != NULL) && tamd_dev_zero(ddi, slots * nb)) ||
+                               ((dme != NULL) && tamd_dev_zero(dme, 2 * slots * ni))))
+                return TAMD_RAISE_DEVICE();
+        const struct tamd_crossings drec = { dpt, ddi, dme, (int)slots };
         if (!paged) { /* every tile resident: the whole traverse in one launch */
                 tamd_geometry_use_begin();
                 rc = tamd_stepper_flatten(stepper, message, sizeof(message));
                 if (rc < 0) rc = TURTLE_RETURN_LIBRARY_ERROR;
                 if ((rc == 0) && tamd_k_traverse(stepper->view, n, dp, dd, altitude_max, max_steps, dix,
-                                     dlen, dst, dcr, stepper->d_stats, stepper->d_stats + 4))
+                                     dlen, dst, dcr, (rec != NULL) ? &drec : NULL, stepper->d_stats,
+                                     stepper->d_stats + 4))
                         rc = TURTLE_RETURN_LIBRARY_ERROR;
                 tamd_geometry_use_end();
                 stepper->last_rounds = 1;
         } else
                 rc = traverse_paged(stepper, n, dp, dd, altitude_max, max_steps, dix, dlen, dst, dcr,
-                    message, sizeof(message));
+                    (rec != NULL) ? &drec : NULL, message, sizeof(message));
         if (rc == TURTLE_RETURN_LIBRARY_ERROR) return TAMD_RAISE_DEVICE();
         if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
         if (tamd_stage_fetch(&st, position, 3 * nb, dp) || tamd_stage_fetch(&st, index, 2 * ni, dix) ||
             tamd_stage_fetch(&st, length, media * nb, dlen) || tamd_stage_fetch(&st, n_steps, ni, dst) ||
-            tamd_stage_fetch(&st, n_crossings, ni, dcr) || tamd_stage_end(&st))
+            tamd_stage_fetch(&st, n_crossings, ni, dcr) ||
+            ((rec != NULL) && (tamd_stage_fetch(&st, rec->point, 3 * slots * nb, dpt) ||
+                                  tamd_stage_fetch(&st, rec->distance, slots * nb, ddi) ||
+                                  tamd_stage_fetch(&st, rec->media, 2 * slots * ni, dme))) ||
+            tamd_stage_end(&st))
                 return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
+}
+
+enum turtle_return turtle_stepper_traverse_n(struct turtle_stepper * stepper, long n,
+    double * position, const double * direction, double altitude_max, int max_steps, int * index,
+    double * length, int * n_steps, int * n_crossings, int space)
+{
+        TAMD_ERROR_INIT(&turtle_stepper_traverse_n);
+        return traverse_n(&error_, stepper, n, position, direction, altitude_max, max_steps, index,
+            length, n_steps, n_crossings, NULL, space);
+}
+
+enum turtle_return turtle_stepper_crossings_n(struct turtle_stepper * stepper, long n,
+    double * position, const double * direction, double altitude_max, int max_steps, int * index,
+    double * length, int * n_steps, int * n_crossings, int capacity, double * point,
+    double * distance, int * media, int space)
+{
+        TAMD_ERROR_INIT(&turtle_stepper_crossings_n);
+        if (n_crossings == NULL) return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
+        if (capacity < 0) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid input parameter(s)");
+        const struct tamd_crossings rec = { point, distance, media, capacity };
+        return traverse_n(&error_, stepper, n, position, direction, altitude_max, max_steps, index,
+            length, n_steps, n_crossings, &rec, space);
 }
 
 int turtle_amd_stepper_rounds(const struct turtle_stepper * stepper) { return stepper->last_rounds; }
