@@ -1,15 +1,96 @@
 #!/bin/bash
-# Instruction mix of the trace kernel variants (cross-compiles; no GPU needed).
+# asm_count.sh [OUT]: every kernel of device.hip as a file of its own, beside the
+# resource table (cross-compiles; no GPU needed).
+#   OUT/device.s          the device-side assembly of the whole file
+#   OUT/kernels/<name>.s  one kernel: its code and its .amdhsa_kernel descriptor, with what
+#                         legitimately differs between two builds of the same code stripped
+#                         (.file, .ident, .loc, the __hip_cuid_<hash> symbol, comments, and the
+#                         function's ordinal in the file that its local labels carry: .LBB<n>_)
+#   OUT/rest.s            everything else, stripped the same way: device functions that were not
+#                         inlined, constant tables, LDS symbols (not the metadata notes, which
+#                         repeat the descriptors in the order the kernels were instantiated in)
+#   OUT/resources.txt     VGPRs, AGPRs, SGPRs, scratch, occupancy, LDS and the instruction mix
+# SRC=<file> compiles another copy of the device layer (the parent's, say) with this tree's
+# headers.  Two builds are then compared with
+#   scripts/asm_diff.py A B          (or: diff -rq A/kernels B/kernels; diff A/rest.s B/rest.s;
+#                                    diff A/resources.txt B/resources.txt)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${1:-/tmp/asm}
-mkdir -p $OUT
-cd $ROOT/turtle_amd/csrc
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -std=c++17 -I../../include -I. \
-    -S --cuda-device-only device.hip -o $OUT/device.s 2>/dev/null
-cd $OUT
-for k in $(grep -oE "^_ZN12_GLOBAL__N_1[0-9]+k_(trace|step)[A-Za-z0-9_]+:" device.s | tr -d ':'); do
-  ln=$(grep -n "^$k:" device.s | head -1 | cut -d: -f1)
-  awk -v s=$ln 'NR>=s{print} NR>s && /s_endpgm/{exit}' device.s > $k.s
-  echo "$k total=$(grep -cE '^\s+[a-z]' $k.s) f64=$(grep -cE '^\s+v_[a-z_0-9]+_f64' $k.s) valu=$(grep -cE '^\s+v_' $k.s) salu=$(grep -cE '^\s+s_' $k.s) vmem=$(grep -cE '^\s+(global|flat|buffer)_' $k.s)"
-done
+SRC=${SRC:-$ROOT/turtle_amd/csrc/device.hip}
+mkdir -p "$OUT"
+rm -rf "$OUT/kernels"
+mkdir "$OUT/kernels"
+/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -std=c++17 \
+    -I"$ROOT/include" -I"$ROOT/turtle_amd/csrc" -S --cuda-device-only "$SRC" -o "$OUT/device.s" \
+    -Rpass-analysis=kernel-resource-usage 2> "$OUT/remarks.txt"
+python3 - "$OUT" <<'EOF'
+import hashlib, re, sys
+out = sys.argv[1]
+strip = re.compile(r'^\s*(;|\.file\b|\.ident\b|\.loc\b)|__hip_cuid_')
+kernels, order, cur, desc, rest = {}, [], None, None, []
+names = set(re.findall(r'^\s*\.amdhsa_kernel\s+(\S+)', open(f'{out}/device.s').read(), re.M))
+symbol, meta = re.compile(r'_Z\w+'), False
+ordinal = re.compile(r'\.L(BB|JTI|func_begin|func_end)\d+')
+for line in open(f'{out}/device.s'):
+    if strip.search(line):
+        continue
+    if '"' not in line:  # (a comment starts at a ';' -- but not inside a string's quotes)
+        line = line.split(';')[0].rstrip() + '\n'
+    line = ordinal.sub(r'.L\1', line)
+    m = re.match(r'^(\S+):', line)
+    if m and m.group(1) in names and cur is None:
+        cur = m.group(1); kernels.setdefault(cur, []); order.append(cur)
+    if cur:
+        kernels[cur].append(line)
+        if line.startswith('.Lfunc_end'):
+            cur = None
+        continue
+    m = re.match(r'^\s*\.amdhsa_kernel\s+(\S+)', line)
+    if m:
+        desc = m.group(1)
+    if desc:
+        kernels.setdefault(desc, []).append(line)
+        if '.end_amdhsa_kernel' in line:
+            desc = None
+        continue
+    # a kernel's own directives (.section, .globl, .type, .size, .set <kernel>.num_vgpr ...) go with
+    # it: kernels come out in the order they were instantiated in, which is not the code's business
+    m = symbol.search(line)
+    if m and m.group(0) in names:
+        kernels.setdefault(m.group(0), []).append(line)
+    elif '.amdgpu_metadata' in line:
+        meta = not meta
+    elif not meta:
+        rest.append(line)
+open(f'{out}/rest.s', 'w').writelines(rest)
+for k, lines in kernels.items():
+    # (hipCUB's kernels have names longer than a file's may be)
+    short = k if len(k) <= 200 else k[:180] + '_' + hashlib.sha1(k.encode()).hexdigest()[:12]
+    open(f'{out}/kernels/{short}.s', 'w').writelines(lines)
+
+res, name = {}, None
+keys = {'VGPRs': 'vgpr', 'AGPRs': 'agpr', 'TotalSGPRs': 'sgpr', 'ScratchSize [bytes/lane]': 'scratch',
+        'Occupancy [waves/SIMD]': 'occ', 'LDS Size [bytes/block]': 'lds'}
+for line in open(f'{out}/remarks.txt'):
+    m = re.search(r'remark: (.*?)\s*\[-Rpass', line)
+    if not m:
+        continue
+    k, _, v = m.group(1).strip().partition(':')
+    if k.strip() == 'Function Name':
+        name = v.strip(); res[name] = {}
+    elif name and k.strip() in keys:
+        res[name][keys[k.strip()]] = v.strip()
+def count(lines, pat):
+    r = re.compile(pat)
+    return sum(1 for l in lines if r.match(l))
+with open(f'{out}/resources.txt', 'w') as f:
+    for k in sorted(order):
+        body = kernels[k][:next(i for i, l in enumerate(kernels[k]) if l.startswith('.Lfunc_end'))]
+        row = ' '.join(f'{a}={b}' for a, b in res.get(k, {}).items())
+        mix = {'total': r'^\s+[a-z]', 'f64': r'^\s+v_[a-z_0-9]+_f64', 'valu': r'^\s+v_', 'salu': r'^\s+s_',
+               'vmem': r'^\s+(global|flat|buffer)_'}
+        f.write(f'{k} {row} ' + ' '.join(f'{a}={count(body, b)}' for a, b in mix.items()) + '\n')
+print(f'{len(order)} kernels -> {out}/kernels, {out}/resources.txt')
+EOF
+grep -E "${KERNELS:-k_(trace|step)}" "$OUT/resources.txt" || true

@@ -41,6 +41,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "internal.h"
 
@@ -1333,6 +1334,16 @@ __device__ __forceinline__ double d_step_length(
         return ds;
 }
 
+/* ---- wave idioms ---------------------------------------------------------
+ *
+ * What the kernels below do a wave at a time. */
+
+/* this lane's rank among the lanes of `mask` (a ballot): how many of them are below it */
+__device__ __forceinline__ int lane_rank(ull mask)
+{
+        return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+}
+
 /* ======================================================================== */
 /*                                 kernels                                  */
 /* ======================================================================== */
@@ -1446,8 +1457,7 @@ __device__ __forceinline__ void page_fault(const Paging & pg, const TileFault & 
         if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(pg.n_faulted, (ull)__popcll(mask));
         base = __shfl(base, leader, 64);
         if (fault) {
-                const int rank = __builtin_amdgcn_mbcnt_hi(
-                    (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+                const int rank = lane_rank(mask);
                 pg.faulted[base + rank] = (int)r;
                 /* the item the host serves without fail: the one it named, else the
                  * first of this list (which it will name from the next round on) */
@@ -1858,8 +1868,7 @@ __device__ __forceinline__ void step_items(const tamd_view & v, long n,
                                         base = atomicAdd(cross.count, (ull)__popcll(mask));
                                 base = __shfl(base, leader, 64);
                                 if (listed) {
-                                        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32),
-                                            __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+                                        const int rank = lane_rank(mask);
                                         cross.ray[base + rank] = (int)r;
                                         cross.ds[base + rank] = listed_ds;
                                 }
@@ -2116,11 +2125,6 @@ struct RayPool {
         int n_free;
         int head[2], count[2];
 };
-
-__device__ __forceinline__ int lane_rank(ull mask)
-{
-        return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-}
 
 /* Two-phase launches.  Steps per ray are heavy-tailed (C2: median 163, max
  * 11 327) and a ray's samples are sequential, so a launch lasts as long as its
@@ -2411,9 +2415,7 @@ __device__ __forceinline__ void trace_body(const tamd_view & v, long n,
                                 continue;
                         }
                         const long avail = pool_end - pool_next;
-                        const int rank = __builtin_amdgcn_mbcnt_hi(
-                            (unsigned)(mask >> 32),
-                            __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+                        const int rank = lane_rank(mask);
                         if (need && (rank < avail)) {
                                 ray = pool_next + rank;
                                 if (ph.ids != nullptr)
@@ -2935,8 +2937,7 @@ __device__ __forceinline__ void trace_body(const tamd_view & v, long n,
                         base_back = __shfl(base_back, leader, 64);
                         if (park) {
                                 const ull mine = back ? bmask : fmask;
-                                const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mine >> 32),
-                                    __builtin_amdgcn_mbcnt_lo((unsigned)mine, 0));
+                                const int rank = lane_rank(mine);
                                 const long place = back ? capacity - 1 - (long)(base_back + rank) : (long)(base + rank);
                                 ph.parked[place] = (int)ray;
                                 if (!MODEL && (ph.sort_key != nullptr)) {
@@ -2976,8 +2977,7 @@ __device__ __forceinline__ void trace_body(const tamd_view & v, long n,
                                         base = atomicAdd(ph.cross.count, (ull)__popcll(cmask));
                                 base = __shfl(base, leader, 64);
                                 if (crossed) {
-                                        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(cmask >> 32),
-                                            __builtin_amdgcn_mbcnt_lo((unsigned)cmask, 0));
+                                        const int rank = lane_rank(cmask);
                                         ph.cross.ray[base + rank] = (int)ray;
                                         ph.cross.ds[base + rank] = ds;
                                         ph.cross.other[base + rank] = cross_pack(bm, bk);
@@ -3280,8 +3280,7 @@ __global__ void __launch_bounds__(256) WALK_WAVES_ATTR k_walk(tamd_view v, long 
                                 continue;
                         }
                         const long avail = pool_end - pool_next;
-                        const int rank = __builtin_amdgcn_mbcnt_hi(
-                            (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+                        const int rank = lane_rank(mask);
                         if (need && (rank < avail)) {
                                 ray = pool_next + rank;
                                 m = index[2 * ray], k = index[2 * ray + 1];
@@ -3441,8 +3440,7 @@ __global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * 
                                 continue;
                         }
                         const long avail = pool_end - pool_next;
-                        const int rank = __builtin_amdgcn_mbcnt_hi(
-                            (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+                        const int rank = lane_rank(mask);
                         if (need && (rank < avail)) {
                                 ray = pool_next + rank;
                                 bx = pos[3 * ray], by = pos[3 * ray + 1], bz = pos[3 * ray + 2];
@@ -4139,6 +4137,22 @@ static int grid_for(long n, int block)
                 if (e_ != hipSuccess) return fail("launch " name, e_);         \
         } while (0)
 
+/* A run-time value that a kernel takes as a template parameter: f is called with the
+ * std::integral_constant of the first of VALUES that equals `value`, or of the last. */
+template <int FIRST, int... REST, class F>
+static int with_constant(int value, F && f)
+{
+        if constexpr (sizeof...(REST) > 0)
+                if (value != FIRST) return with_constant<REST...>(value, f);
+        return f(std::integral_constant<int, FIRST>());
+}
+/* ... the geometry's MODE (one map, one stack, else the generic instance) */
+template <class F>
+static int with_mode(int mode, F && f)
+{
+        return with_constant<TAMD_MODE_ONE_MAP, TAMD_MODE_ONE_STACK, TAMD_MODE_GENERIC>(mode, f);
+}
+
 extern "C" int tamd_k_ecef_from_geodetic(long n, const double * lat,
     const double * lon, const double * elev, double * ecef)
 {
@@ -4241,38 +4255,31 @@ static int run_step(struct tamd_view view, long n, double * pos, const double * 
 {
         const dim3 grid(grid_for(n, 256)), block(256);
         const bool strict = g_math_strict || !view.fast_ok;
-#define STEP_CASE(MODE)                                                                        \
-        do {                                                                                   \
-                if (strict)                                                                    \
-                        hipLaunchKernelGGL((k_step<MODE, false>), grid, block, 0, g_stream, view, n,   \
-                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk); \
-                else if (MODE == TAMD_MODE_GENERIC)                                            \
-                        hipLaunchKernelGGL((k_step<MODE, true>), grid, block, 0, g_stream, view, n,    \
-                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk); \
-                else                                                                           \
-                        hipLaunchKernelGGL((k_step_fast<MODE>), grid, block, 0, g_stream, view, n,     \
-                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk); \
-                LAUNCH_CHECK("k_step");                                                        \
-                if (cross.ray == nullptr) break;                                               \
-                /* the listed rays are a few percent of n, and their number is on the        \
-                 * device: a grid for a tenth of n, striding over whatever there is */         \
-                const dim3 few(grid_for(n / 10 + 1, 256));                                     \
-                if (strict)                                                                    \
-                        hipLaunchKernelGGL((k_bisect<MODE, false>), few, block, 0, g_stream, view,     \
-                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk); \
-                else                                                                           \
-                        hipLaunchKernelGGL((k_bisect<MODE, true>), few, block, 0, g_stream, view,      \
-                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk); \
-                LAUNCH_CHECK("k_bisect");                                                      \
-        } while (0)
-        if (view.mode == TAMD_MODE_ONE_MAP)
-                STEP_CASE(TAMD_MODE_ONE_MAP);
-        else if (view.mode == TAMD_MODE_ONE_STACK)
-                STEP_CASE(TAMD_MODE_ONE_STACK);
-        else
-                STEP_CASE(TAMD_MODE_GENERIC);
-#undef STEP_CASE
-        return 0;
+        return with_mode(view.mode, [&](auto mode) {
+                constexpr int MODE = decltype(mode)::value;
+                if (strict)
+                        hipLaunchKernelGGL((k_step<MODE, false>), grid, block, 0, g_stream, view, n,
+                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk);
+                else if (MODE == TAMD_MODE_GENERIC)
+                        hipLaunchKernelGGL((k_step<MODE, true>), grid, block, 0, g_stream, view, n,
+                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk);
+                else
+                        hipLaunchKernelGGL((k_step_fast<MODE>), grid, block, 0, g_stream, view, n,
+                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk);
+                LAUNCH_CHECK("k_step");
+                if (cross.ray == nullptr) return 0;
+                /* the listed rays are a few percent of n, and their number is on the
+                 * device: a grid for a tenth of n, striding over whatever there is */
+                const dim3 few(grid_for(n / 10 + 1, 256));
+                if (strict)
+                        hipLaunchKernelGGL((k_bisect<MODE, false>), few, block, 0, g_stream, view,
+                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk);
+                else
+                        hipLaunchKernelGGL((k_bisect<MODE, true>), few, block, 0, g_stream, view,
+                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk);
+                LAUNCH_CHECK("k_bisect");
+                return 0;
+        });
 }
 
 extern "C" int tamd_k_step(struct tamd_view view, long n, double * pos,
@@ -4289,8 +4296,7 @@ extern "C" int tamd_k_step(struct tamd_view view, long n, double * pos,
 
 /* Waves per SIMD the trace kernel is launched with.  It is fp64-VALU bound
  * with a dependent 4-node gather per sample, so a few waves per SIMD are
- * enough to cover the gather latency; TURTLE_AMD_TRACE_WAVES overrides the
- * default for experiments. */
+ * enough to cover the gather latency: as many as fit. */
 static int trace_blocks_per_cu(const void * kernel)
 {
         int blocks = 0;
@@ -4303,20 +4309,7 @@ static int trace_blocks_per_cu(const void * kernel)
          * in flight: 2.38 -> 2.29 ms a pass over 10 passes, 2.39 -> 2.18 over 20; C4 25.5 -> 24.7;
          * through a stack no change -- two blocks a CU whatever fits: C2 the same, C4 24.1, but C3
          * 23.9 -> 25.3; alone a kernel would lose either way: C2 3.55 -> 3.7 with two) */
-        if ((g_ctx.in_flight > 1) && (blocks > 2)) {
-                static int share = -1; /* experiments: 0: as many as fit, 1: one fewer, 2: two */
-                if (share < 0) {
-                        const char * e = getenv("TURTLE_AMD_IN_FLIGHT_SHARE");
-                        share = ((e != nullptr) && (*e != 0)) ? atoi(e) : 1;
-                }
-                if (share == 1) blocks -= 1;
-                if (share == 2) blocks = 2;
-        }
-        const char * env = getenv("TURTLE_AMD_TRACE_WAVES");
-        if ((env != nullptr) && (*env != 0)) {
-                const int waves = atoi(env); /* per SIMD == blocks of 256 per CU */
-                if ((waves >= 1) && (waves < blocks)) blocks = waves;
-        }
+        if ((g_ctx.in_flight > 1) && (blocks > 2)) blocks -= 1;
         return blocks;
 }
 
@@ -4338,14 +4331,8 @@ static int launch_trace_(struct tamd_view view, long n, bool n_on_device, double
                 /* phase B: the rays phase A handed over -- the long ones (a few
                  * percent of n) and whatever was in flight when its queue ran dry
                  * (up to one ray per lane): as many blocks as fit, or as there can
-                 * be work for (TURTLE_AMD_TAIL_DIV: fewer, for experiments) */
-                static int div = 0;
-                if (div == 0) {
-                        const char * env = getenv("TURTLE_AMD_TAIL_DIV");
-                        div = ((env != nullptr) && (*env != 0)) ? atoi(env) : 1;
-                        if (div < 1) div = 1;
-                }
-                long wide = useful / div;
+                 * be work for */
+                long wide = useful;
                 if (wide < (long)g_cus) wide = (long)g_cus;
                 if (blocks > wide) blocks = wide;
         }
@@ -4409,11 +4396,23 @@ static int launch_cross(struct tamd_view view, long n, double * pos, const doubl
         return 0;
 }
 
-static int env_int(const char * name, int fallback)
-{
-        const char * env = getenv(name);
-        return ((env != nullptr) && (*env != 0)) ? atoi(env) : fallback;
-}
+/* A run-time knob: an environment variable holding a number, read once per process;
+ * `fallback` where it is unset or empty. */
+struct Knob {
+        const char * name;
+        long fallback;
+        bool read = false;
+        long value = 0;
+        long get()
+        {
+                if (!read) {
+                        const char * env = getenv(name);
+                        value = ((env != nullptr) && (*env != 0)) ? atol(env) : fallback;
+                        read = true;
+                }
+                return value;
+        }
+};
 
 /* Step counts at which a ray moves on to the next phase of a fast trace (0: no
  * further phase), and the rays a wave of phase A may still hold when it hands
@@ -4424,11 +4423,10 @@ static int env_int(const char * name, int fallback)
  * (a stack, 10 M rays) from 42.4 to 39.8 ms -- the last only with the stack's lined
  * kernel at three waves a SIMD (trace_waves(); at two, 47.5).  Layered geometries
  * have no lean loop. */
-static int park_threshold(int mode, long n)
+static int park_threshold(int mode)
 {
-        static int value = -2;
-        (void)n;
-        if (value == -2) value = env_int("TURTLE_AMD_PARK", -1);
+        static Knob knob = { "TURTLE_AMD_PARK", -1 };
+        const int value = (int)knob.get();
         if (value >= 0) return value;
         return (mode == TAMD_MODE_GENERIC) ? 512 : 32;
 }
@@ -4438,23 +4436,21 @@ static int park_threshold(int mode, long n)
  * C3, 10 M: 42.6 -> 41.8).  The loop gives the same bits whenever it engages. */
 static int creep_lanes(long n)
 {
-        static int value = -2;
-        if (value == -2) value = env_int("TURTLE_AMD_CREEP_LANES", -1);
+        static Knob knob = { "TURTLE_AMD_CREEP_LANES", -1 };
+        const int value = (int)knob.get();
         if (value >= 0) return value;
         return (n >= 2000000) ? 4 * kCreepLanes : kCreepLanes;
 }
 static int dense_go(void)
 {
-        static int value = -1;
-        if (value < 0) value = env_int("TURTLE_AMD_DENSE_GO", 24);
-        return value;
+        static Knob knob = { "TURTLE_AMD_DENSE_GO", 24 };
+        return (int)knob.get();
 }
 /* What phase A takes for a long ray when it sorts its hand-over (see there; 0: unsorted) */
 static int sort_long_if(void)
 {
-        static int value = -1;
-        if (value < 0) value = env_int("TURTLE_AMD_SORT_LONG", 120);
-        return value;
+        static Knob knob = { "TURTLE_AMD_SORT_LONG", 120 };
+        return (int)knob.get();
 }
 /* Do the lined pass's waves exchange rays through LDS (RayPool)?  The same bits either way
  * (test_ray_pool_changes_no_bit); what it is worth, measured (round 4, one MI355X, each alone):
@@ -4466,22 +4462,18 @@ static int sort_long_if(void)
  * TURTLE_AMD_POOL=0 / 1: never / wherever the kernel exists. */
 static int pool_on(int mode, long n)
 {
-        static int value = -2;
-        if (value == -2) value = env_int("TURTLE_AMD_POOL", -1);
+        static Knob knob = { "TURTLE_AMD_POOL", -1 };
+        const int value = (int)knob.get();
         if (value >= 0) return value;
         return (mode == TAMD_MODE_ONE_MAP) && (n >= 6000000);
 }
 /* Is the hand-over ordered between the passes (run_trace)?  A batch of a few million rays is as
  * long as its longest rays' own chains, and drawing those first is worth more than the sort costs
  * (TURTLE_AMD_SORT_KEY: 0 never, 1 always, else up to that many rays). */
-static int sort_hand_over(int mode, long n)
+static int sort_hand_over(long n)
 {
-        static long value = -2;
-        (void)mode;
-        if (value == -2) {
-                const char * env = getenv("TURTLE_AMD_SORT_KEY");
-                value = ((env != nullptr) && (*env != 0)) ? atol(env) : -1;
-        }
+        static Knob knob = { "TURTLE_AMD_SORT_KEY", -1 };
+        const long value = knob.get();
         if (value == 0) return 0;
         if (value == 1) return 1;
         return n <= ((value > 1) ? value : 4000000L);
@@ -4490,28 +4482,22 @@ static int sort_hand_over(int mode, long n)
  * 0 never, 1 always, else from that many rays on. */
 static int spatial_order(int mode, long n)
 {
-        static long value = -2;
-        if (value == -2) {
-                const char * env = getenv("TURTLE_AMD_SPATIAL");
-                value = ((env != nullptr) && (*env != 0)) ? atol(env) : -1;
-        }
+        static Knob knob = { "TURTLE_AMD_SPATIAL", -1 };
+        const long value = knob.get();
         if ((mode == TAMD_MODE_GENERIC) || (value == 0)) return 0;
         if (value == 1) return 1;
         /* (measured, one pass alone, off -> on: one map at 1 / 2 / 4 / 12.5 M rays 3.13 -> 3.20, 5.91 ->
          * 5.95, 11.17 -> 10.92, 26.7 -> 26.3 ms; a 4 x 4 stack at 1 / 10 M rays 4.10 -> 4.10, 25.5 -> 22.8) */
         return n >= ((value > 1) ? value : 3000000L);
 }
+/* phase A hands over when its queue is dry and a wave is down to this many rays (PhaseIO.drain_lanes;
+ * 0: never, as in the passes that have nobody to hand over to): 64, so any wave does */
+constexpr int kDrainLanes = 64;
 /* the room behind the lists of a trace (internal.h, TAMD_TRACE_SORT_ROOM), on a 256-byte boundary */
 static char * sort_room_of(int * parked, long n)
 {
         const uintptr_t at = (uintptr_t)(parked + TAMD_TRACE_SORT_INTS * n);
         return (char *)((at + 255) & ~(uintptr_t)255);
-}
-static int drain_lanes(void)
-{
-        static int value = -1;
-        if (value < 0) value = env_int("TURTLE_AMD_DRAIN", 64);
-        return value;
 }
 
 /* One round of a trace: all the rays (pg.ids == NULL), or the ones the last
@@ -4564,14 +4550,14 @@ static int run_trace(struct tamd_view view, long n, double * pos, const double *
                         return 1;
                 return launch_cross<MODE, false>(view, n, pos, dir, index, length, n_steps, cross, pg, stats);
         }
-        const int park = park_threshold(MODE, n);
+        const int park = park_threshold(MODE);
         if ((park <= 0) || (max_steps <= park)) {
                 if (launch_trace<MODE, true, false>(view, n, again, pos, dir, max_steps, index, length,
                         n_steps, flags, one, stats, queue))
                         return 1;
                 return launch_cross<MODE, true>(view, n, pos, dir, index, length, n_steps, cross, pg, stats);
         }
-        PhaseIO a = { pg.ids, pg.n_in, parked, queue + 2 * kQ, park, resume, pg, drain_lanes(), 0,
+        PhaseIO a = { pg.ids, pg.n_in, parked, queue + 2 * kQ, park, resume, pg, kDrainLanes, 0,
                 kChunk, creep_lanes(n), dense_go(), cross };
         PhaseIO b = { parked, queue + 2 * kQ, nullptr, nullptr, 0, 1, pg, 0, park, kChunk,
                 creep_lanes(n), dense_go(), cross };
@@ -4635,7 +4621,7 @@ static int run_trace(struct tamd_view view, long n, double * pos, const double *
                         }
                 }
         }
-        const bool order = sort_room && !again && (a.n_parked_back != nullptr) && sort_hand_over(MODE, n);
+        const bool order = sort_room && !again && (a.n_parked_back != nullptr) && sort_hand_over(n);
         hipcub::DoubleBuffer<unsigned char> keys((unsigned char *)(parked + 5 * n), (unsigned char *)(parked + 6 * n));
         hipcub::DoubleBuffer<int> ids(parked, parked + 4 * n);
         void * const sort_temp = (void *)sort_room_of(parked, n);
@@ -4690,14 +4676,10 @@ extern "C" int tamd_k_trace(struct tamd_view view, long n, double * pos,
         if (n <= 0) return 0;
         const int carry = ((flags & TURTLE_AMD_TRACE_RESUME) ? TRACE_CARRY_MEDIUM : 0) |
             ((parked != nullptr) ? (flags & TAMD_TRACE_SORT_ROOM) : 0);
-        if (view.mode == TAMD_MODE_ONE_MAP)
-                return run_trace<TAMD_MODE_ONE_MAP>(view, n, pos, dir, max_steps, index, length,
+        return with_mode(view.mode, [&](auto mode) {
+                return run_trace<decltype(mode)::value>(view, n, pos, dir, max_steps, index, length,
                     n_steps, carry, parked, cross_ds, pg, stats, queue);
-        if (view.mode == TAMD_MODE_ONE_STACK)
-                return run_trace<TAMD_MODE_ONE_STACK>(view, n, pos, dir, max_steps, index, length,
-                    n_steps, carry, parked, cross_ds, pg, stats, queue);
-        return run_trace<TAMD_MODE_GENERIC>(view, n, pos, dir, max_steps, index, length, n_steps,
-            carry, parked, cross_ds, pg, stats, queue);
+        });
 }
 
 /* n single steps with a direction, in two passes (see k_step); cross_ray /
@@ -4746,29 +4728,22 @@ extern "C" int tamd_k_walk(struct tamd_view view, long n, double * pos, double *
         if (n <= 0) return 0;
         const WalkIO io = { seed, first, first_step, n_steps };
         const bool strict = g_math_strict || !view.fast_ok;
-#define WALK_CASE(MODE)                                                                        \
-        do {                                                                                   \
-                const void * kernel = strict ? (const void *)k_walk<MODE, false> :            \
-                                               (const void *)k_walk<MODE, true>;               \
-                long blocks = (long)g_cus * trace_blocks_per_cu(kernel);                       \
-                const long useful = (n + 255) / 256;                                           \
-                if (blocks > useful) blocks = useful;                                          \
-                if (strict)                                                                    \
-                        hipLaunchKernelGGL((k_walk<MODE, false>), dim3((unsigned)blocks), dim3(256), 0,   \
-                            g_stream, view, n, pos, alt, elev, index, length, steps, io, stats, queue);  \
-                else                                                                           \
-                        hipLaunchKernelGGL((k_walk<MODE, true>), dim3((unsigned)blocks), dim3(256), 0,    \
-                            g_stream, view, n, pos, alt, elev, index, length, steps, io, stats, queue);  \
-        } while (0)
-        if (view.mode == TAMD_MODE_ONE_MAP)
-                WALK_CASE(TAMD_MODE_ONE_MAP);
-        else if (view.mode == TAMD_MODE_ONE_STACK)
-                WALK_CASE(TAMD_MODE_ONE_STACK);
-        else
-                WALK_CASE(TAMD_MODE_GENERIC);
-#undef WALK_CASE
-        LAUNCH_CHECK("k_walk");
-        return 0;
+        return with_mode(view.mode, [&](auto mode) {
+                constexpr int MODE = decltype(mode)::value;
+                const void * kernel = strict ? (const void *)k_walk<MODE, false> :
+                                               (const void *)k_walk<MODE, true>;
+                long blocks = (long)g_cus * trace_blocks_per_cu(kernel);
+                const long useful = (n + 255) / 256;
+                if (blocks > useful) blocks = useful;
+                if (strict)
+                        hipLaunchKernelGGL((k_walk<MODE, false>), dim3((unsigned)blocks), dim3(256), 0,
+                            g_stream, view, n, pos, alt, elev, index, length, steps, io, stats, queue);
+                else
+                        hipLaunchKernelGGL((k_walk<MODE, true>), dim3((unsigned)blocks), dim3(256), 0,
+                            g_stream, view, n, pos, alt, elev, index, length, steps, io, stats, queue);
+                LAUNCH_CHECK("k_walk");
+                return 0;
+        });
 }
 
 template <int MODE, bool REC>
@@ -4799,23 +4774,16 @@ extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, cons
         if (n <= 0) return 0;
         const TraverseIO io = { dir, length, n_steps, n_cross, ceiling, max_steps };
         const bool strict = g_math_strict || !view.fast_ok;
-#define TRAVERSE_CASE(MODE)                                                                    \
-        do {                                                                                   \
-                if (rec != nullptr)                                                            \
-                        launch_traverse<MODE, true>(view, n, pos, index, io, stats, queue, strict, *rec); \
-                else                                                                           \
-                        launch_traverse<MODE, false>(view, n, pos, index, io, stats, queue, strict, \
-                            NoCrossings());                                                    \
-        } while (0)
-        if (view.mode == TAMD_MODE_ONE_MAP)
-                TRAVERSE_CASE(TAMD_MODE_ONE_MAP);
-        else if (view.mode == TAMD_MODE_ONE_STACK)
-                TRAVERSE_CASE(TAMD_MODE_ONE_STACK);
-        else
-                TRAVERSE_CASE(TAMD_MODE_GENERIC);
-#undef TRAVERSE_CASE
-        LAUNCH_CHECK("k_traverse");
-        return 0;
+        return with_mode(view.mode, [&](auto mode) {
+                constexpr int MODE = decltype(mode)::value;
+                if (rec != nullptr)
+                        launch_traverse<MODE, true>(view, n, pos, index, io, stats, queue, strict, *rec);
+                else
+                        launch_traverse<MODE, false>(view, n, pos, index, io, stats, queue, strict,
+                            NoCrossings());
+                LAUNCH_CHECK("k_traverse");
+                return 0;
+        });
 }
 
 /* One generation of a paged traverse: as tamd_k_step_dir with TURTLE_AMD_STEP_RESUME, the
@@ -4907,23 +4875,15 @@ extern "C" int tamd_k_resample(struct tamd_view view, const struct tamd_grid * g
         struct tamd_grid target;
         if (tamd_dev_d2h(&target, grids, sizeof(target))) return 1;
         const dim3 blocks(grid_for(n_blocks * 64, 256));
-#define RS_LAUNCH(S, P)                                                                            \
-        hipLaunchKernelGGL((k_resample<S, P>), blocks, dim3(256), 0, g_stream, view, grids, z0, dz,      \
-            is_signed, flags, n_blocks, out, pg, counters)
-#define RS_LAUNCH_ALL(S)                                                                           \
-        do {                                                                                       \
-                if (target.proj.type == TAMD_PROJ_LAMBERT) RS_LAUNCH(S, TAMD_PROJ_LAMBERT);        \
-                else if (target.proj.type == TAMD_PROJ_UTM) RS_LAUNCH(S, TAMD_PROJ_UTM);           \
-                else RS_LAUNCH(S, TAMD_PROJ_NONE);                                                 \
-        } while (0)
-        if (from_map)
-                RS_LAUNCH_ALL(RS_MAP);
-        else
-                RS_LAUNCH_ALL(RS_STACK);
-#undef RS_LAUNCH_ALL
-#undef RS_LAUNCH
-        LAUNCH_CHECK("k_resample");
-        return 0;
+        return with_constant<RS_MAP, RS_STACK>(from_map ? RS_MAP : RS_STACK, [&](auto source) {
+                return with_constant<TAMD_PROJ_LAMBERT, TAMD_PROJ_UTM, TAMD_PROJ_NONE>(target.proj.type, [&](auto type) {
+                        hipLaunchKernelGGL((k_resample<decltype(source)::value, decltype(type)::value>), blocks,
+                            dim3(256), 0, g_stream, view, grids, z0, dz, is_signed, flags, n_blocks, out, pg,
+                            counters);
+                        LAUNCH_CHECK("k_resample");
+                        return 0;
+                });
+        });
 }
 
 extern "C" int tamd_k_unblock(const uint16_t * blocked, int nx, int ny, int nbx, uint16_t * rows)
