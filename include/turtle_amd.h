@@ -525,6 +525,35 @@ TURTLE_API enum turtle_return turtle_stepper_trace_n(
     int * index /* [n][2] */, double * length, int * n_steps, int flags,
     int space);
 
+/* ---- the stepper inside the caller's own kernel (turtle_amd_device.h) ----------------
+ *
+ * turtle_amd_stepper_view_acquire lends a kernel the stepper's geometry: it flattens the
+ * stepper for the calling thread's device, brings every tile of every stack into memory (as
+ * turtle_stack_load does), copies a `struct turtle_amd_view` (turtle_amd_device.h) to `view`
+ * and keeps everything the view points at where it is until
+ * turtle_amd_stepper_view_release(stepper), called by the same thread.  `size` is the caller's
+ * sizeof(struct turtle_amd_view): the library refuses a view that is not laid out as its own
+ * (turtle_amd_view_layout gives the library's version and size).
+ *   BAD_ADDRESS    stepper or view is NULL
+ *   DOMAIN_ERROR   `size` is not the library's; the view is out already; a stack's stack_size
+ *                  is below the number of its tiles (the device side does not page)
+ *   LIBRARY_ERROR  no usable device ("no HIP device is visible ...")
+ * Ordering is the caller's: the library's own work is ordered on the thread's stream
+ * (turtle_amd_stream_set, turtle_amd_synchronize); the acquire returns with the tables in
+ * place, the caller's kernels may be launched on any stream after it returns, and must have
+ * FINISHED before the release.
+ * While a thread holds a view, batch calls over resident geometry work as ever (on that
+ * stepper too).  What would change the geometry fails in the holding thread with DOMAIN_ERROR
+ * instead of waiting for its own view: turtle_map_fill, turtle_map_resample,
+ * turtle_stack_clear / _load, turtle_map_destroy / turtle_stack_destroy (through the handler;
+ * the object stays), a batch call that has to page tiles in, and, on the stepper itself,
+ * turtle_stepper_add_* and turtle_stepper_destroy.  Other threads that would change it wait
+ * for the release, as they wait for a batch call.  Releasing what is not held: DOMAIN_ERROR. */
+TURTLE_API enum turtle_return turtle_amd_stepper_view_acquire(
+    struct turtle_stepper * stepper, void * view, size_t size);
+TURTLE_API enum turtle_return turtle_amd_stepper_view_release(struct turtle_stepper * stepper);
+TURTLE_API void turtle_amd_view_layout(int * version, size_t * size);
+
 /* Number of media of the stepper's geometry: its layers + 1 (index[0] ranges
  * over [0, media)). */
 TURTLE_API int turtle_amd_stepper_media(const struct turtle_stepper * stepper);

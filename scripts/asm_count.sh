@@ -10,6 +10,9 @@
 #                         inlined, constant tables, LDS symbols (not the metadata notes, which
 #                         repeat the descriptors in the order the kernels were instantiated in)
 #   OUT/resources.txt     VGPRs, AGPRs, SGPRs, scratch, occupancy, LDS and the instruction mix
+# RENAME="old=new old2=new2": symbol prefixes replaced in every line before the split (device functions
+# and constant tables that moved to another namespace keep their code and change their mangled names:
+# the kernels that call them then differ from the older build in those names alone).
 # SRC=<file> compiles another copy of the device layer (the parent's, say) with this tree's
 # headers.  Two builds are then compared with
 #   scripts/asm_diff.py A B          (or: diff -rq A/kernels B/kernels; diff A/rest.s B/rest.s;
@@ -25,8 +28,9 @@ mkdir "$OUT/kernels"
     -I"$ROOT/include" -I"$ROOT/turtle_amd/csrc" -S --cuda-device-only "$SRC" -o "$OUT/device.s" \
     -Rpass-analysis=kernel-resource-usage 2> "$OUT/remarks.txt"
 python3 - "$OUT" <<'EOF'
-import hashlib, re, sys
+import hashlib, os, re, sys
 out = sys.argv[1]
+rename = [p.split('=', 1) for p in os.environ.get('RENAME', '').split()]
 strip = re.compile(r'^\s*(;|\.file\b|\.ident\b|\.loc\b)|__hip_cuid_')
 kernels, order, cur, desc, rest = {}, [], None, None, []
 names = set(re.findall(r'^\s*\.amdhsa_kernel\s+(\S+)', open(f'{out}/device.s').read(), re.M))
@@ -38,6 +42,8 @@ for line in open(f'{out}/device.s'):
     if '"' not in line:  # (a comment starts at a ';' -- but not inside a string's quotes)
         line = line.split(';')[0].rstrip() + '\n'
     line = ordinal.sub(r'.L\1', line)
+    for old, new in rename:
+        line = line.replace(old, new)
     m = re.match(r'^(\S+):', line)
     if m and m.group(1) in names and cur is None:
         cur = m.group(1); kernels.setdefault(cur, []); order.append(cur)

@@ -462,6 +462,28 @@ class Stack:
 
 # ---- stepper -----------------------------------------------------------------
 
+def view_layout():
+    """(version, size) of the library's struct turtle_amd_view"""
+    version, size = C.c_int(), C.c_size_t()
+    lib().turtle_amd_view_layout(C.byref(version), C.byref(size))
+    return version.value, size.value
+
+
+class _View:
+    def __init__(self, stepper):
+        self.stepper = stepper
+
+    def __enter__(self):
+        size = view_layout()[1]
+        buf = C.create_string_buffer(size)
+        _check(lib().turtle_amd_stepper_view_acquire(self.stepper.h, buf, C.c_size_t(size)))
+        return buf.raw
+
+    def __exit__(self, *exc):
+        _check(lib().turtle_amd_stepper_view_release(self.stepper.h))
+        return False
+
+
 class Stepper:
     """struct turtle_stepper handle: same verbs as the C API."""
 
@@ -660,6 +682,12 @@ class Stepper:
                                                 _ptr(distance), _ptr(media), sp))
         return dict(position=pos, index=index, length=length, n_steps=nsteps,
                     n_crossings=ncross, point=point, distance=distance, media=media)
+
+    def view(self):
+        """turtle_amd_stepper_view_acquire / _release as a context manager: `with st.view() as v`
+        gives the bytes of the struct turtle_amd_view to hand to a kernel built on
+        include/turtle_amd_device.h; the geometry stays put until the block ends."""
+        return _View(self)
 
     def trace_into(self, pos, d, index, length, nsteps, max_steps=100000):
         """Device-resident trace with caller-owned tensors (no allocation):

@@ -80,6 +80,17 @@ void tamd_geometry_use_end(void);
 /* ... and whoever may free tiles or maps holds it exclusively, plus the lock */
 void tamd_geometry_write_begin(void);
 void tamd_geometry_write_end(void);
+/* A device view (turtle_amd_stepper_view_acquire) keeps the geometry in use until its release:
+ * views the calling THREAD holds.  That thread cannot take the geometry exclusively meanwhile (it
+ * would wait for itself): whatever would, fails first with TAMD_VIEW_HELD_TEXT. */
+int tamd_geometry_view_held(void);
+void tamd_geometry_view_hold(int delta);
+#define TAMD_VIEW_HELD_TEXT "the calling thread holds a device view of a stepper (turtle_amd_stepper_view_release comes first)"
+#define TAMD_VIEW_GUARD()                                                      \
+        do {                                                                   \
+                if (tamd_geometry_view_held())                                 \
+                        return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, TAMD_VIEW_HELD_TEXT); \
+        } while (0)
 /* frees the HBM copies of a map (inside write_begin / _end) once what is queued on
  * their devices has run */
 void tamd_map_release(struct turtle_map * map);
@@ -263,6 +274,8 @@ struct turtle_stepper {
         double * d_scratch_ds;        /* ... and one double each (same block) */
         long parked_capacity;
         int last_rounds;              /* rounds the last batch call took (1: nothing was paged in) */
+        int view_out;                 /* a device view of it is out (turtle_amd_stepper_view_acquire): its
+                                       * tables stay as they are until the release */
 };
 
 /* Any change to what kernels may read (map nodes, tiles, layers) bumps the epoch

@@ -16,106 +16,12 @@
 #include <stdint.h>
 
 #include "turtle_amd.h"
+#include "turtle_amd_device.h" /* the POD tables read by the kernels */
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-/* ------------------------------------------------------------------------ */
-/* POD tables read by the kernels (layout shared by host and device code)   */
-/* ------------------------------------------------------------------------ */
-
-/* One DEM grid resident in HBM: 16-bit nodes, native little-endian, in BLOCKS
- * of 8 x 8 nodes (128 bytes, one cache line; rows south->north inside a block
- * and from block to block, nbx blocks per block row, the grid padded to whole
- * blocks): node (ix, iy) is at ((iy / 8) * nbx + ix / 8) * 64 + (iy % 8) * 8 +
- * ix % 8.  A sample reads the 2 x 2 nodes of a cell; in rows of nx nodes those
- * are two lines 2 nx bytes apart, in blocks one line three times out of four,
- * and the next cells of the ray -- whichever way it heads -- are in it too.
- * Decoding the file format (byte order, row flip, sign) happens ONCE at upload
- * instead of per node access as the reference's get_z callbacks do [ref
- * src/turtle/map.h:47-49, io/hgt.c:127-131, map.c:41-44]; integers are exact,
- * so parity is unaffected.  z = z0 + v * dz with v read as int16 if is_signed
- * else uint16 (signed codecs use z0 = 0, dz = 1, which reproduces "(int16)v"
- * exactly). */
-#define TAMD_BLOCK 8
-/* A map projection [ref src/turtle/projection.h:29-46]; type < 0: geodetic */
-enum tamd_proj_type { TAMD_PROJ_NONE = -1, TAMD_PROJ_LAMBERT = 0, TAMD_PROJ_UTM = 1 };
-
-struct tamd_proj {
-        int type;           /* enum tamd_proj_type */
-        int lambert_tag;    /* 0..5: I, II, IIe, III, IV, 93 */
-        double longitude_0; /* UTM central meridian, degrees */
-        int hemisphere;     /* UTM: +1 north, -1 south */
-        int pad_;
-};
-
-struct tamd_grid {
-        const uint16_t * nodes;
-        int nx, ny;
-        double x0, y0, dx, dy;
-        double z0, dz;
-        double inv_dx, inv_dy; /* 1/dx, 1/dy: the fast-math kernels multiply */
-        int is_signed;
-        int nbx; /* blocks of TAMD_BLOCK x TAMD_BLOCK nodes per block row */
-        struct tamd_proj proj; /* x, y of a projected map; the stepper projects
-                                * (latitude, longitude) first [ref stepper.c:243-248] */
-};
-
-/* Tile directory of a stack [ref src/turtle/stack.h:32-49]: O(1) lookup
- * replaces the reference's MRU list scan [ref stack.c:300-335]. */
-struct tamd_stack {
-        double lat0, lon0, dlat, dlon;
-        double inv_dlat, inv_dlon; /* the fast-math lookup multiplies (seams: exact) */
-        int nlat, nlon;
-        int tile_first; /* offset into the tiles[] table: grid index or -1 */
-        /* `regular`: every tile present has the same shape and encoding (nx,
-         * ny, dx, dy, z0, dz, sign) and sits exactly on the lattice (x0 ==
-         * lon0 + ix*dlon, y0 == lat0 + iy*dlat) whose cell it spans ((nx-1) dx
-         * == dlon up to rounding), as SRTM/ASTER tiles do.  The
-         * fast-math kernels then need one pointer per tile (slot_nodes[
-         * nodes_first + slot], NULL for a missing tile) instead of a whole
-         * per-lane grid descriptor; `proto` holds the shared shape. */
-        int regular;
-        int nodes_first, pad_;
-        struct tamd_grid proto;
-};
-
-enum tamd_kind { TAMD_FLAT = 0, TAMD_MAP = 1, TAMD_STACK = 2 };
-
-/* values of the tile table (tamd_view.tiles) besides a grid index */
-#define TAMD_TILE_NONE (-1)  /* no file for this slot */
-#define TAMD_TILE_PAGED (-2) /* a file, not resident: see "Paging" in device.hip */
-
-/* One (data, offset) entry of a layer [ref src/turtle/stepper.h:80-85], stored
- * in the reference's iteration order: last added first [ref stepper.c:722-724] */
-struct tamd_meta {
-        int kind; /* enum tamd_kind */
-        int src;  /* grid index (MAP) or stack index (STACK) */
-        double offset;
-};
-
-enum tamd_mode {
-        TAMD_MODE_GENERIC = 0,   /* any layers / data / geoid */
-        TAMD_MODE_ONE_MAP = 1,   /* one layer, one geodetic map, no geoid */
-        TAMD_MODE_ONE_STACK = 2  /* one layer, one stack, no geoid */
-};
-
-/* Everything a kernel needs about a stepper, passed BY VALUE as a kernel
- * argument so that it sits in scalar registers. */
-struct tamd_view {
-        const struct tamd_grid * grids;
-        const struct tamd_stack * stacks;
-        const int * tiles;
-        const uint16_t * const * slot_nodes; /* see tamd_stack.regular */
-        const struct tamd_meta * metas;
-        const int * layer_first; /* n_layers + 1 offsets into metas */
-        int n_layers;
-        int geoid; /* grid index or -1 */
-        double slope, resolution;
-        int mode; /* enum tamd_mode */
-        int fast_ok; /* every grid has nx, ny >= 2: the clamped fast lookup applies */
-};
 
 /* ------------------------------------------------------------------------ */
 /* Device layer (device.hip).  Every function returns 0 on success or a     */

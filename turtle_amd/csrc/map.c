@@ -38,6 +38,10 @@ void tamd_geometry_changed(void) { __atomic_add_fetch(&g_epoch, 1, __ATOMIC_ACQ_
 void tamd_geometry_use_begin(void) { pthread_rwlock_rdlock(&g_use); }
 void tamd_geometry_use_end(void) { pthread_rwlock_unlock(&g_use); }
 
+static __thread int t_views = 0;
+int tamd_geometry_view_held(void) { return t_views; }
+void tamd_geometry_view_hold(int delta) { t_views += delta; }
+
 /* Whoever may FREE HBM copies holds the geometry exclusively: first against its
  * users (no thread between building its tables and queueing its launches), then
  * the lock (always in that order; nested in one thread: the outermost counts). */
@@ -111,6 +115,11 @@ void turtle_map_destroy(struct turtle_map ** map)
 {
         if ((map == NULL) || (*map == NULL)) return;
         struct turtle_map * m = *map;
+        if (tamd_geometry_view_held()) { /* (through the handler: the map stays) */
+                TAMD_ERROR_INIT(&turtle_map_destroy);
+                TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, TAMD_VIEW_HELD_TEXT);
+                return;
+        }
         tamd_geometry_write_begin();
         if (m->stack != NULL) { /* a tile leaves its stack */
                 struct turtle_stack * s = m->stack;
@@ -225,6 +234,7 @@ enum turtle_return turtle_map_fill(
     struct turtle_map * map, int ix, int iy, double elevation)
 {
         TAMD_ERROR_INIT(&turtle_map_fill);
+        TAMD_VIEW_GUARD();
         if (map == NULL)
                 return TAMD_RAISE(
                     TURTLE_RETURN_MEMORY_ERROR, "could not allocate memory");

@@ -136,6 +136,7 @@ enum turtle_return turtle_map_resample(struct turtle_map * map, struct turtle_st
     const struct turtle_map * source, int flags, long * outside, long * clamped)
 {
         TAMD_ERROR_INIT(&turtle_map_resample);
+        TAMD_VIEW_GUARD();
         if ((map == NULL) || ((stack == NULL) && (source == NULL)))
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
         if ((stack != NULL) && (source != NULL))

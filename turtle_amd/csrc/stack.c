@@ -300,6 +300,11 @@ void turtle_stack_destroy(struct turtle_stack ** stack)
 {
         if ((stack == NULL) || (*stack == NULL)) return;
         struct turtle_stack * s = *stack;
+        if (tamd_geometry_view_held()) { /* (through the handler: the stack stays) */
+                TAMD_ERROR_INIT(&turtle_stack_destroy);
+                TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, TAMD_VIEW_HELD_TEXT);
+                return;
+        }
         stack_release_tiles(s);
         const int n = s->latitude_n * s->longitude_n;
         int i;
@@ -313,6 +318,7 @@ void turtle_stack_destroy(struct turtle_stack ** stack)
 enum turtle_return turtle_stack_clear(struct turtle_stack * stack)
 {
         TAMD_ERROR_INIT(&turtle_stack_clear);
+        TAMD_VIEW_GUARD();
         if ((stack->lock != NULL) && (stack->lock() != 0))
                 return TAMD_RAISE(TURTLE_RETURN_LOCK_ERROR, "could not acquire the lock");
         stack_release_tiles(stack);
@@ -342,6 +348,7 @@ void tamd_stack_trim(struct turtle_stack * s)
 {
         const int n = s->latitude_n * s->longitude_n, budget = tamd_stack_budget(s);
         int i;
+        if (tamd_geometry_view_held()) return; /* (nothing came in: tamd_stack_page_in refuses then) */
         if (s->lock != NULL) (void)s->lock();
         tamd_geometry_write_begin();
         for (i = 0; i < n; i++)
@@ -470,6 +477,10 @@ static int stack_page_in(struct turtle_stack * s, const unsigned * wanted,
 int tamd_stack_page_in(struct turtle_stack * s, const unsigned * wanted,
     const unsigned * wanted_first, int first_bit, int few, char * message, size_t size)
 {
+        if (tamd_geometry_view_held()) { /* (bringing tiles in takes the geometry exclusively) */
+                snprintf(message, size, TAMD_VIEW_HELD_TEXT);
+                return -TURTLE_RETURN_DOMAIN_ERROR;
+        }
         if ((s->lock != NULL) && (s->lock() != 0)) {
                 snprintf(message, size, "could not acquire the lock");
                 return -TURTLE_RETURN_LOCK_ERROR;
@@ -574,6 +585,10 @@ int tamd_stack_host_fetch(struct turtle_stack * s, int slot, double latitude, do
     double * z, int * inside, char * message, size_t size)
 {
         const int n = s->latitude_n * s->longitude_n, budget = tamd_stack_budget(s);
+        if (tamd_geometry_view_held()) {
+                snprintf(message, size, TAMD_VIEW_HELD_TEXT);
+                return TURTLE_RETURN_DOMAIN_ERROR;
+        }
         if ((s->lock != NULL) && (s->lock() != 0)) {
                 snprintf(message, size, "could not acquire the lock");
                 return TURTLE_RETURN_LOCK_ERROR;
@@ -611,6 +626,7 @@ int tamd_stack_host_fetch(struct turtle_stack * s, int slot, double latitude, do
 enum turtle_return turtle_stack_load(struct turtle_stack * stack)
 {
         TAMD_ERROR_INIT(&turtle_stack_load);
+        TAMD_VIEW_GUARD();
         if ((stack->latitude_n == 0) || (stack->longitude_n == 0))
                 return TURTLE_RETURN_SUCCESS;
         if ((stack->lock != NULL) && (stack->lock() != 0))

@@ -19,6 +19,12 @@
 #include <string.h>
 
 /* what the stepper holds in HBM, on the device it was last used on */
+#define VIEW_OUT_TEXT "a device view of the stepper is out (turtle_amd_stepper_view_release comes first)"
+#define VIEW_OUT_GUARD(stepper)                                                \
+        do {                                                                   \
+                if ((stepper)->view_out) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, VIEW_OUT_TEXT); \
+        } while (0)
+
 static void stepper_release_device(struct turtle_stepper * s)
 {
         int drained = 1;
@@ -66,6 +72,10 @@ enum turtle_return turtle_stepper_destroy(struct turtle_stepper ** stepper)
 {
         if ((stepper == NULL) || (*stepper == NULL)) return TURTLE_RETURN_SUCCESS;
         struct turtle_stepper * s = *stepper;
+        if (s->view_out) {
+                TAMD_ERROR_INIT(&turtle_stepper_destroy);
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, VIEW_OUT_TEXT);
+        }
         int i;
         for (i = 0; i < s->n_data; i++) /* owned clients [ref stepper.c:578-586] */
                 if (s->data[i].client != NULL) turtle_client_destroy(&s->data[i].client);
@@ -96,6 +106,7 @@ static int push_layer(struct turtle_stepper * s)
 enum turtle_return turtle_stepper_add_layer(struct turtle_stepper * stepper)
 {
         TAMD_ERROR_INIT(&turtle_stepper_add_layer);
+        VIEW_OUT_GUARD(stepper);
         if (push_layer(stepper))
                 return TAMD_RAISE(TURTLE_RETURN_MEMORY_ERROR, "could not allocate memory");
         return TURTLE_RETURN_SUCCESS;
@@ -139,6 +150,7 @@ enum turtle_return turtle_stepper_add_stack(
     struct turtle_stepper * stepper, struct turtle_stack * stack, double offset)
 {
         TAMD_ERROR_INIT(&turtle_stepper_add_stack);
+        VIEW_OUT_GUARD(stepper);
         int i, data = -1;
         for (i = 0; i < stepper->n_data; i++)
                 if ((stepper->data[i].kind == TAMD_STACK) && (stepper->data[i].stack == stack))
@@ -166,6 +178,7 @@ enum turtle_return turtle_stepper_add_map(
     struct turtle_stepper * stepper, struct turtle_map * map, double offset)
 {
         TAMD_ERROR_INIT(&turtle_stepper_add_map);
+        VIEW_OUT_GUARD(stepper);
         int i, data = -1;
         for (i = 0; i < stepper->n_data; i++)
                 if ((stepper->data[i].kind == TAMD_MAP) && (stepper->data[i].map == map))
@@ -183,6 +196,7 @@ enum turtle_return turtle_stepper_add_map(
 enum turtle_return turtle_stepper_add_flat(struct turtle_stepper * stepper, double offset)
 {
         TAMD_ERROR_INIT(&turtle_stepper_add_flat);
+        VIEW_OUT_GUARD(stepper);
         int i, data = -1;
         for (i = 0; i < stepper->n_data; i++)
                 if (stepper->data[i].kind == TAMD_FLAT) data = i;
@@ -319,6 +333,9 @@ int tamd_stepper_flatten(struct turtle_stepper * s, char * message, size_t size)
         }
         s->view.slope = s->slope_factor;
         s->view.resolution = s->resolution_factor;
+        /* a view of it is out: the tables it names stay (nothing they point at can go meanwhile:
+         * the view holds the geometry in use) */
+        if (s->view_out && (s->d_tables != NULL)) return 0;
         if ((s->epoch == tamd_geometry_epoch_get()) && (s->d_tables != NULL)) return 0;
         /* the lists of tiles are read, and maps uploaded, under the lock */
         tamd_geometry_lock();
@@ -599,6 +616,74 @@ static int stepper_rounds(struct turtle_stepper * stepper, long n, stepper_round
                         if (stepper->data[i].kind == TAMD_STACK) tamd_stack_trim(stepper->data[i].stack);
         }
         return rc;
+}
+
+/* ---- a device view: the geometry lent to the caller's own kernel ------------- */
+
+void turtle_amd_view_layout(int * version, size_t * size)
+{
+        if (version != NULL) *version = TURTLE_AMD_VIEW_VERSION;
+        if (size != NULL) *size = sizeof(struct turtle_amd_view);
+}
+
+enum turtle_return turtle_amd_stepper_view_acquire(struct turtle_stepper * stepper, void * view, size_t size)
+{
+        TAMD_ERROR_INIT(&turtle_amd_stepper_view_acquire);
+        if ((stepper == NULL) || (view == NULL))
+                return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
+        if (size != sizeof(struct turtle_amd_view))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
+                    "the view is %zu bytes, this library's is %zu (version %d): build the caller with this "
+                    "library's turtle_amd_device.h", size, sizeof(struct turtle_amd_view), TURTLE_AMD_VIEW_VERSION);
+        if (stepper->view_out) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "the stepper's view is out already");
+        if (tamd_dev_init()) return TAMD_RAISE_DEVICE();
+        /* every tile of every stack in memory (turtle_stack_load), before the span begins */
+        char message[4200];
+        int i;
+        for (i = 0; i < stepper->n_data; i++) {
+                if (stepper->data[i].kind != TAMD_STACK) continue;
+                struct turtle_stack * st = stepper->data[i].stack;
+                if (tamd_stack_budget(st) < st->n_files)
+                        return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
+                            "a stack of %d tiles cannot keep them all in memory (stack_size %d): a device view "
+                            "names resident tiles only", st->n_files, st->max_size);
+                if (st->n_loaded >= st->n_files) continue;
+                TAMD_VIEW_GUARD(); /* (loading takes what another view of this thread holds) */
+                const enum turtle_return rc = turtle_stack_load(st);
+                if (rc != TURTLE_RETURN_SUCCESS) return rc;
+        }
+        tamd_geometry_use_begin();
+        int rc = tamd_stepper_flatten(stepper, message, sizeof(message));
+        int paged = 0;
+        if (rc == 0) paged = stepper_is_paged(stepper); /* (a tile another thread took meanwhile) */
+        if ((rc != 0) || paged) {
+                tamd_geometry_use_end();
+                if (rc < 0) return TAMD_RAISE_DEVICE();
+                if (rc > 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "a tile left its stack while the view was made: try again");
+        }
+        struct turtle_amd_view out;
+        memset(&out, 0, sizeof(out));
+        out.geometry = stepper->view;
+        out.version = TURTLE_AMD_VIEW_VERSION;
+        out.size = (int)sizeof(out);
+        memcpy(view, &out, sizeof(out));
+        stepper->view_out = 1;
+        tamd_geometry_view_hold(+1);
+        return TURTLE_RETURN_SUCCESS;
+}
+
+enum turtle_return turtle_amd_stepper_view_release(struct turtle_stepper * stepper)
+{
+        TAMD_ERROR_INIT(&turtle_amd_stepper_view_release);
+        if (stepper == NULL) return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
+        if (!stepper->view_out || (tamd_geometry_view_held() == 0))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
+                    "no device view of the stepper is held by the calling thread");
+        stepper->view_out = 0;
+        tamd_geometry_view_hold(-1);
+        tamd_geometry_use_end();
+        return TURTLE_RETURN_SUCCESS;
 }
 
 #define FLATTEN_OR_RETURN(stepper)                                             \
