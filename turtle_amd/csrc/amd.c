@@ -55,18 +55,14 @@ enum turtle_return turtle_amd_tally_n(long n, const int * index, const double * 
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
         if ((n_media < 0) || (n_bins < 1) || !(length_max > 0.))
                 return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid input parameter(s)");
-        struct tamd_stage st;
+        struct tamd_stage st = { 0 };
         void *dix, *dlen, *dh, *dg;
-        const size_t hb = (size_t)(n_media + 1) * sizeof(*hits);
-        const size_t gb = (size_t)(n_bins + 1) * sizeof(*histogram);
-        if (tamd_stage_begin(&st, space,
-                (size_t)n * (sizeof(double) + 2 * sizeof(int)) + hb + gb) ||
-            tamd_stage_in(&st, index, 2 * (size_t)n * sizeof(int), &dix) ||
-            tamd_stage_in(&st, length, (size_t)n * sizeof(double), &dlen) ||
-            tamd_stage_in(&st, hits, hb, &dh) || tamd_stage_in(&st, histogram, gb, &dg) ||
-            tamd_k_tally(n, dix, dlen, n_media, dh, n_bins, length_max, dg) ||
-            tamd_stage_fetch(&st, hits, hb, dh) || tamd_stage_fetch(&st, histogram, gb, dg) ||
-            tamd_stage_end(&st))
+        tamd_stage_add(&st, index, 2 * (size_t)n * sizeof(int), TAMD_IN, &dix);
+        tamd_stage_add(&st, length, (size_t)n * sizeof(double), TAMD_IN, &dlen);
+        tamd_stage_add(&st, hits, (size_t)(n_media + 1) * sizeof(*hits), TAMD_INOUT, &dh);
+        tamd_stage_add(&st, histogram, (size_t)(n_bins + 1) * sizeof(*histogram), TAMD_INOUT, &dg);
+        if (tamd_stage_open(&st, space) ||
+            tamd_k_tally(n, dix, dlen, n_media, dh, n_bins, length_max, dg) || tamd_stage_close(&st))
                 return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
 }
@@ -75,13 +71,12 @@ enum turtle_return turtle_amd_philox_n(long n, unsigned long long seed,
     unsigned long long stream, long first_ray, unsigned int * words, int space)
 {
         TAMD_ERROR_INIT(&turtle_amd_philox_n);
-        struct tamd_stage st;
+        struct tamd_stage st = { 0 };
         void * dw;
-        const size_t bytes = (size_t)n * 4 * sizeof(unsigned int);
         if (words == NULL) return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
-        if (tamd_stage_begin(&st, space, bytes) || tamd_stage_out(&st, words, bytes, &dw) ||
-            tamd_k_philox(n, seed, stream, first_ray, dw) ||
-            tamd_stage_fetch(&st, words, bytes, dw) || tamd_stage_end(&st))
+        tamd_stage_add(&st, words, (size_t)n * 4 * sizeof(unsigned int), TAMD_OUT, &dw);
+        if (tamd_stage_open(&st, space) || tamd_k_philox(n, seed, stream, first_ray, dw) ||
+            tamd_stage_close(&st))
                 return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
 }
@@ -90,14 +85,13 @@ enum turtle_return turtle_amd_isotropic_n(long n, unsigned long long seed,
     unsigned long long stream, long first_ray, double * direction, int space)
 {
         TAMD_ERROR_INIT(&turtle_amd_isotropic_n);
-        struct tamd_stage st;
+        struct tamd_stage st = { 0 };
         void * dd;
-        const size_t bytes = (size_t)n * 3 * sizeof(double);
         if (direction == NULL)
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
-        if (tamd_stage_begin(&st, space, bytes) || tamd_stage_out(&st, direction, bytes, &dd) ||
-            tamd_k_isotropic(n, seed, stream, first_ray, dd) ||
-            tamd_stage_fetch(&st, direction, bytes, dd) || tamd_stage_end(&st))
+        tamd_stage_add(&st, direction, (size_t)n * 3 * sizeof(double), TAMD_OUT, &dd);
+        if (tamd_stage_open(&st, space) || tamd_k_isotropic(n, seed, stream, first_ray, dd) ||
+            tamd_stage_close(&st))
                 return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
 }

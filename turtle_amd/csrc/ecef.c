@@ -13,15 +13,46 @@ static int run4(int (*kernel)(long, const double *, const double *, const double
     long n, const double * a, const double * b, const double * c, const double * d,
     size_t out_doubles, double * out, int space)
 {
-        struct tamd_stage st;
+        struct tamd_stage st = { 0 };
         void *da, *db, *dc, *dd, *dout;
         const size_t nb = (size_t)n * sizeof(double);
-        return tamd_stage_begin(&st, space, (4 + out_doubles) * nb) ||
-            tamd_stage_in(&st, a, nb, &da) || tamd_stage_in(&st, b, nb, &db) ||
-            tamd_stage_in(&st, c, nb, &dc) || tamd_stage_in(&st, d, nb, &dd) ||
-            tamd_stage_out(&st, out, out_doubles * nb, &dout) ||
-            kernel(n, da, db, dc, dd, dout) ||
-            tamd_stage_fetch(&st, out, out_doubles * nb, dout) || tamd_stage_end(&st);
+        tamd_stage_add(&st, a, nb, TAMD_IN, &da);
+        tamd_stage_add(&st, b, nb, TAMD_IN, &db);
+        tamd_stage_add(&st, c, nb, TAMD_IN, &dc);
+        tamd_stage_add(&st, d, nb, TAMD_IN, &dd);
+        tamd_stage_add(&st, out, out_doubles * nb, TAMD_OUT, &dout);
+        return tamd_stage_open(&st, space) || kernel(n, da, db, dc, dd, dout) || tamd_stage_close(&st);
+}
+
+static int run_to_geodetic(long n, const double * ecef, double * latitude, double * longitude,
+    double * altitude, int space)
+{
+        struct tamd_stage st = { 0 };
+        void *de, *dla, *dlo, *dal;
+        const size_t nb = (size_t)n * sizeof(double);
+        tamd_stage_add(&st, ecef, 3 * nb, TAMD_IN, &de);
+        tamd_stage_add(&st, latitude, nb, TAMD_OUT, &dla);
+        tamd_stage_add(&st, longitude, nb, TAMD_OUT, &dlo);
+        tamd_stage_add(&st, altitude, nb, TAMD_OUT, &dal);
+        return tamd_stage_open(&st, space) || tamd_k_ecef_to_geodetic(n, de, dla, dlo, dal) ||
+            tamd_stage_close(&st);
+}
+
+static int run_to_horizontal(long n, const double * latitude, const double * longitude,
+    const double * direction, double * azimuth, double * elevation, int space)
+{
+        struct tamd_stage st = { 0 };
+        void *dla, *dlo, *dd, *daz, *del;
+        const size_t nb = (size_t)n * sizeof(double);
+        tamd_stage_add(&st, latitude, nb, TAMD_IN, &dla);
+        tamd_stage_add(&st, longitude, nb, TAMD_IN, &dlo);
+        tamd_stage_add(&st, direction, 3 * nb, TAMD_IN, &dd);
+        /* outputs are read-modify-write: a null direction leaves them untouched
+         * [ref ecef.c:194] */
+        tamd_stage_add(&st, azimuth, nb, TAMD_INOUT, &daz);
+        tamd_stage_add(&st, elevation, nb, TAMD_INOUT, &del);
+        return tamd_stage_open(&st, space) || tamd_k_ecef_to_horizontal(n, dla, dlo, dd, daz, del) ||
+            tamd_stage_close(&st);
 }
 
 static int k_from_geodetic(long n, const double * lat, const double * lon,
@@ -55,18 +86,7 @@ enum turtle_return turtle_ecef_to_geodetic_n(long n, const double * ecef,
     double * latitude, double * longitude, double * altitude, int space)
 {
         TAMD_ERROR_INIT(&turtle_ecef_to_geodetic_n);
-        struct tamd_stage st;
-        void *de, *dla, *dlo, *dal;
-        const size_t nb = (size_t)n * sizeof(double);
-        if (tamd_stage_begin(&st, space, 6 * nb) || tamd_stage_in(&st, ecef, 3 * nb, &de) ||
-            tamd_stage_out(&st, latitude, nb, &dla) ||
-            tamd_stage_out(&st, longitude, nb, &dlo) ||
-            tamd_stage_out(&st, altitude, nb, &dal) ||
-            tamd_k_ecef_to_geodetic(n, de, dla, dlo, dal) ||
-            tamd_stage_fetch(&st, latitude, nb, dla) ||
-            tamd_stage_fetch(&st, longitude, nb, dlo) ||
-            tamd_stage_fetch(&st, altitude, nb, dal) || tamd_stage_end(&st))
-                return TAMD_RAISE_DEVICE();
+        if (run_to_geodetic(n, ecef, latitude, longitude, altitude, space)) return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
 }
 
@@ -75,18 +95,7 @@ enum turtle_return turtle_ecef_to_horizontal_n(long n, const double * latitude,
     double * elevation, int space)
 {
         TAMD_ERROR_INIT(&turtle_ecef_to_horizontal_n);
-        struct tamd_stage st;
-        void *dla, *dlo, *dd, *daz, *del;
-        const size_t nb = (size_t)n * sizeof(double);
-        /* outputs are read-modify-write: a null direction leaves them untouched
-         * [ref ecef.c:194] */
-        if (tamd_stage_begin(&st, space, 7 * nb) || tamd_stage_in(&st, latitude, nb, &dla) ||
-            tamd_stage_in(&st, longitude, nb, &dlo) ||
-            tamd_stage_in(&st, direction, 3 * nb, &dd) ||
-            tamd_stage_in(&st, azimuth, nb, &daz) || tamd_stage_in(&st, elevation, nb, &del) ||
-            tamd_k_ecef_to_horizontal(n, dla, dlo, dd, daz, del) ||
-            tamd_stage_fetch(&st, azimuth, nb, daz) ||
-            tamd_stage_fetch(&st, elevation, nb, del) || tamd_stage_end(&st))
+        if (run_to_horizontal(n, latitude, longitude, direction, azimuth, elevation, space))
                 return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
 }
@@ -134,17 +143,7 @@ void turtle_ecef_to_geodetic(
                 if (altitude != NULL) *altitude = al;
                 return;
         }
-        struct tamd_stage st;
-        void *de, *dla, *dlo, *dal;
-        if (tamd_stage_begin(&st, TURTLE_AMD_HOST, 6 * sizeof(double)) ||
-            tamd_stage_in(&st, ecef, 3 * sizeof(double), &de) ||
-            tamd_stage_out(&st, latitude, sizeof(double), &dla) ||
-            tamd_stage_out(&st, longitude, sizeof(double), &dlo) ||
-            tamd_stage_out(&st, altitude, sizeof(double), &dal) ||
-            tamd_k_ecef_to_geodetic(1, de, dla, dlo, dal) ||
-            tamd_stage_fetch(&st, latitude, sizeof(double), dla) ||
-            tamd_stage_fetch(&st, longitude, sizeof(double), dlo) ||
-            tamd_stage_fetch(&st, altitude, sizeof(double), dal) || tamd_stage_end(&st))
+        if (run_to_geodetic(1, ecef, latitude, longitude, altitude, TURTLE_AMD_HOST))
                 raise_void((turtle_function_t *)&turtle_ecef_to_geodetic);
 }
 
@@ -155,16 +154,6 @@ void turtle_ecef_to_horizontal(double latitude, double longitude,
                 tamd_h_to_horizontal(latitude, longitude, direction, azimuth, elevation);
                 return;
         }
-        struct tamd_stage st;
-        void *dla, *dlo, *dd, *daz, *del;
-        if (tamd_stage_begin(&st, TURTLE_AMD_HOST, 7 * sizeof(double)) ||
-            tamd_stage_in(&st, &latitude, sizeof(double), &dla) ||
-            tamd_stage_in(&st, &longitude, sizeof(double), &dlo) ||
-            tamd_stage_in(&st, direction, 3 * sizeof(double), &dd) ||
-            tamd_stage_in(&st, azimuth, sizeof(double), &daz) ||
-            tamd_stage_in(&st, elevation, sizeof(double), &del) ||
-            tamd_k_ecef_to_horizontal(1, dla, dlo, dd, daz, del) ||
-            tamd_stage_fetch(&st, azimuth, sizeof(double), daz) ||
-            tamd_stage_fetch(&st, elevation, sizeof(double), del) || tamd_stage_end(&st))
+        if (run_to_horizontal(1, &latitude, &longitude, direction, azimuth, elevation, TURTLE_AMD_HOST))
                 raise_void((turtle_function_t *)&turtle_ecef_to_horizontal);
 }

@@ -276,6 +276,8 @@ struct turtle_stepper {
         int last_rounds;              /* rounds the last batch call took (1: nothing was paged in) */
         int view_out;                 /* a device view of it is out (turtle_amd_stepper_view_acquire): its
                                        * tables stay as they are until the release */
+        char message[4200];           /* why the last call failed, until it is raised (one stepper
+                                       * is one stream of calls) */
 };
 
 /* Any change to what kernels may read (map nodes, tiles, layers) bumps the epoch
@@ -303,25 +305,42 @@ void tamd_pager_end(struct tamd_pager * pager);
 #define TAMD_PAGING_ROUNDS 100000 /* a batch needs about one round per tile it touches */
 
 /* ---- HOST/DEVICE array staging for the batch calls ----------------------- */
-#define TAMD_STAGE_PENDING 12
+/* An entry point names each of its arrays ONCE, with a direction:
+ *
+ *      struct tamd_stage st = { 0 };
+ *      tamd_stage_add(&st, latitude, nb, TAMD_IN, &args.lat);      (declare: nothing happens yet)
+ *      tamd_stage_add(&st, position, 3 * nb, TAMD_INOUT, &args.pos);
+ *      if (tamd_stage_open(&st, space)) ...         (sizes the arena, copies IN and INOUT arrays in)
+ *      ... launches on args.lat, args.pos ...
+ *      if (tamd_stage_close(&st)) ...               (brings OUT and INOUT arrays back; HOST: waits)
+ *
+ * The open writes the address the kernels use into `*dev`: the user's own pointer in DEVICE space
+ * and for a NULL array (neither copied nor brought back), a piece of the thread's arena in HOST
+ * space.  The close reads `*dev` again: a caller may put another address there in between.
+ * A variant of a call is a direction chosen at the declaration, not a second list.  TAMD_TABLE is
+ * a host blob of the library's own that the kernels of this call read (a one-grid view): in the
+ * arena in either space, and the close then waits in either space, before the arena is reused.
+ * At most TAMD_STAGE_ARRAYS declarations; one more makes the open fail.  An error between open
+ * and close just returns: nothing is held. */
+enum { TAMD_IN = 1, TAMD_OUT = 2, TAMD_INOUT = 3, TAMD_TABLE = 5 };
+#define TAMD_STAGE_ARRAYS 12
 struct tamd_stage {
+        int n;               /* arrays declared so far: starts from { 0 } */
         int space;
         int packed;          /* small HOST call: through the thread's pinned buffer (stage.c) */
-        int n_pending;
+        int wait;            /* something is in the arena, or the space is HOST: the close waits */
         char * pinned;
         size_t pinned_used;
-        struct {
+        struct tamd_stage_array {
                 void * user;
-                const void * dev;
+                void ** dev;
                 size_t bytes;
-        } pending[TAMD_STAGE_PENDING]; /* outputs to bring back: tamd_stage_end does, in one copy */
+                int dir;
+        } array[TAMD_STAGE_ARRAYS];
 };
-int tamd_stage_begin(struct tamd_stage * st, int space, size_t total_bytes);
-/* returns the device address to use for a user array (NULL stays NULL) */
-int tamd_stage_in(struct tamd_stage * st, const void * user, size_t bytes, void ** dev);
-int tamd_stage_out(struct tamd_stage * st, void * user, size_t bytes, void ** dev);
-int tamd_stage_fetch(struct tamd_stage * st, void * user, size_t bytes, const void * dev);
-int tamd_stage_end(struct tamd_stage * st);
+void tamd_stage_add(struct tamd_stage * st, const void * user, size_t bytes, int dir, void ** dev);
+int tamd_stage_open(struct tamd_stage * st, int space);
+int tamd_stage_close(struct tamd_stage * st);
 
 /* ---- the scalar entry points on the host (scalar.c; opt-in) ------------------- */
 int tamd_scalar_on_host(void);

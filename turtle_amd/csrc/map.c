@@ -7,6 +7,7 @@
 
 #include <math.h>
 #include <pthread.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -408,51 +409,48 @@ int tamd_map_sync(struct turtle_map * map, struct tamd_grid * grid)
         return 0;
 }
 
-/* A one-grid view for the elevation kernel: tables live in the scratch arena */
-static int map_view(struct turtle_map * map, struct tamd_view * view)
+/* A one-grid view for the elevation kernels: its tables go to the arena with the call's arrays
+ * (a TAMD_TABLE of its stage) */
+struct map_tables {
+        struct tamd_grid grid;
+        struct tamd_meta meta;
+};
+
+static int map_tables(struct turtle_map * map, struct map_tables * tables)
 {
-        struct {
-                struct tamd_grid grid;
-                struct tamd_meta meta;
-        } tables;
-        memset(&tables, 0, sizeof(tables));
-        if (tamd_map_sync(map, &tables.grid)) return 1;
-        tables.meta.kind = TAMD_MAP;
-        void * dev;
-        if (tamd_scratch_get(&dev, sizeof(tables))) return 1;
-        if (tamd_dev_h2d(dev, &tables, sizeof(tables))) return 1;
-        memset(view, 0, sizeof(*view));
-        view->grids = (const struct tamd_grid *)dev;
-        view->metas = (const struct tamd_meta *)((char *)dev + sizeof(struct tamd_grid));
-        view->n_layers = 1;
-        view->geoid = -1;
-        return 0;
+        memset(tables, 0, sizeof(*tables));
+        tables->meta.kind = TAMD_MAP;
+        return tamd_map_sync(map, &tables->grid);
 }
+
+static struct tamd_view map_view(const void * dev)
+{
+        struct tamd_view view;
+        memset(&view, 0, sizeof(view));
+        view.grids = (const struct tamd_grid *)dev;
+        view.metas = (const struct tamd_meta *)((const char *)dev + offsetof(struct map_tables, meta));
+        view.n_layers = 1;
+        view.geoid = -1;
+        return view;
+}
+
+static const struct tamd_paging no_paging = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, -1 };
 
 static int map_elevation_n(struct turtle_map * map, long n, const double * x,
     const double * y, double * elevation, int * inside, int space)
 {
-        struct tamd_stage st;
-        struct tamd_view view;
-        void *dx, *dy, *dz, *di;
+        struct tamd_stage st = { 0 };
+        struct map_tables tables;
+        void *dt, *dx, *dy, *dz, *di;
         const size_t nb = (size_t)n * sizeof(double);
-        if (tamd_stage_begin(&st, space, 3 * nb + n * sizeof(int) + 4096)) return 1;
-        if (space == TURTLE_AMD_DEVICE) tamd_scratch_reset();
-        if (map_view(map, &view)) return 1;
-        if (tamd_stage_in(&st, x, nb, &dx) || tamd_stage_in(&st, y, nb, &dy) ||
-            tamd_stage_out(&st, elevation, nb, &dz) ||
-            tamd_stage_out(&st, inside, n * sizeof(int), &di))
-                return 1;
-        {
-                const struct tamd_paging none = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, -1 };
-                if (tamd_k_elevation(view, n, dx, dy, dz, di, none)) return 1;
-        }
-        if (tamd_stage_fetch(&st, elevation, nb, dz) ||
-            tamd_stage_fetch(&st, inside, n * sizeof(int), di))
-                return 1;
-        /* the one-grid tables sit in the scratch arena: finish before reuse */
-        if (tamd_stage_end(&st)) return 1;
-        return tamd_dev_sync();
+        if (map_tables(map, &tables)) return 1;
+        tamd_stage_add(&st, &tables, sizeof(tables), TAMD_TABLE, &dt);
+        tamd_stage_add(&st, x, nb, TAMD_IN, &dx);
+        tamd_stage_add(&st, y, nb, TAMD_IN, &dy);
+        tamd_stage_add(&st, elevation, nb, TAMD_OUT, &dz);
+        tamd_stage_add(&st, inside, n * sizeof(int), TAMD_OUT, &di);
+        return tamd_stage_open(&st, space) || tamd_k_elevation(map_view(dt), n, dx, dy, dz, di, no_paging) ||
+            tamd_stage_close(&st);
 }
 
 enum turtle_return turtle_map_elevation_n(const struct turtle_map * map, long n,
@@ -491,27 +489,20 @@ enum turtle_return turtle_map_elevation(const struct turtle_map * map, double x,
 static int map_gradient_n(struct turtle_map * map, long n, const double * x,
     const double * y, double * gx, double * gy, int * inside, int space)
 {
-        struct tamd_stage st;
-        struct tamd_view view;
-        void *dx, *dy, *dgx, *dgy, *di;
+        struct tamd_stage st = { 0 };
+        struct map_tables tables;
+        void *dt, *dx, *dy, *dgx, *dgy, *di;
         const size_t nb = (size_t)n * sizeof(double);
-        if (tamd_stage_begin(&st, space, 4 * nb + n * sizeof(int) + 4096)) return 1;
-        if (space == TURTLE_AMD_DEVICE) tamd_scratch_reset();
-        if (map_view(map, &view)) return 1;
+        if (map_tables(map, &tables)) return 1;
+        tamd_stage_add(&st, &tables, sizeof(tables), TAMD_TABLE, &dt);
+        tamd_stage_add(&st, x, nb, TAMD_IN, &dx);
+        tamd_stage_add(&st, y, nb, TAMD_IN, &dy);
         /* gx, gy are in-out: a point outside the map leaves them untouched */
-        if (tamd_stage_in(&st, x, nb, &dx) || tamd_stage_in(&st, y, nb, &dy) ||
-            tamd_stage_in(&st, gx, nb, &dgx) || tamd_stage_in(&st, gy, nb, &dgy) ||
-            tamd_stage_out(&st, inside, n * sizeof(int), &di))
-                return 1;
-        {
-                const struct tamd_paging none = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, -1 };
-                if (tamd_k_gradient(view, n, dx, dy, dgx, dgy, di, none)) return 1;
-        }
-        if (tamd_stage_fetch(&st, gx, nb, dgx) || tamd_stage_fetch(&st, gy, nb, dgy) ||
-            tamd_stage_fetch(&st, inside, n * sizeof(int), di))
-                return 1;
-        if (tamd_stage_end(&st)) return 1;
-        return tamd_dev_sync();
+        tamd_stage_add(&st, gx, nb, TAMD_INOUT, &dgx);
+        tamd_stage_add(&st, gy, nb, TAMD_INOUT, &dgy);
+        tamd_stage_add(&st, inside, n * sizeof(int), TAMD_OUT, &di);
+        return tamd_stage_open(&st, space) ||
+            tamd_k_gradient(map_view(dt), n, dx, dy, dgx, dgy, di, no_paging) || tamd_stage_close(&st);
 }
 
 enum turtle_return turtle_map_gradient_n(const struct turtle_map * map, long n,

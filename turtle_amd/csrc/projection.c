@@ -146,16 +146,17 @@ void tamd_projection_desc(const struct turtle_projection * projection, struct ta
 static int project_n(const struct turtle_projection * projection, int inverse, long n,
     const double * a, const double * b, double * c, double * d, int space)
 {
-        struct tamd_stage st;
+        struct tamd_stage st = { 0 };
         struct tamd_proj desc;
         void *da, *db, *dc, *dd;
         const size_t nb = (size_t)n * sizeof(double);
         tamd_projection_desc(projection, &desc);
-        return tamd_stage_begin(&st, space, 4 * nb) || tamd_stage_in(&st, a, nb, &da) ||
-            tamd_stage_in(&st, b, nb, &db) || tamd_stage_out(&st, c, nb, &dc) ||
-            tamd_stage_out(&st, d, nb, &dd) || tamd_k_project(desc, inverse, n, da, db, dc, dd) ||
-            tamd_stage_fetch(&st, c, nb, dc) || tamd_stage_fetch(&st, d, nb, dd) ||
-            tamd_stage_end(&st);
+        tamd_stage_add(&st, a, nb, TAMD_IN, &da);
+        tamd_stage_add(&st, b, nb, TAMD_IN, &db);
+        tamd_stage_add(&st, c, nb, TAMD_OUT, &dc);
+        tamd_stage_add(&st, d, nb, TAMD_OUT, &dd);
+        return tamd_stage_open(&st, space) || tamd_k_project(desc, inverse, n, da, db, dc, dd) ||
+            tamd_stage_close(&st);
 }
 
 static enum turtle_return check(struct tamd_error * error, const struct turtle_projection * p)

@@ -780,21 +780,18 @@ static int stack_elevation_n(struct turtle_stack * stack, long n,
     const double * latitude, const double * longitude, double * elevation,
     int * inside, int space, char * message, size_t size)
 {
-        struct tamd_stage st;
+        struct tamd_stage st = { 0 };
         void *da, *db, *dz, *di;
         const size_t nb = (size_t)n * sizeof(double);
-        if (tamd_stage_begin(&st, space, 3 * nb + n * sizeof(int))) return -1;
-        if (tamd_stage_in(&st, latitude, nb, &da) || tamd_stage_in(&st, longitude, nb, &db) ||
-            tamd_stage_out(&st, elevation, nb, &dz) ||
-            tamd_stage_out(&st, inside, n * sizeof(int), &di))
-                return -1;
+        tamd_stage_add(&st, latitude, nb, TAMD_IN, &da);
+        tamd_stage_add(&st, longitude, nb, TAMD_IN, &db);
+        tamd_stage_add(&st, elevation, nb, TAMD_OUT, &dz);
+        tamd_stage_add(&st, inside, n * sizeof(int), TAMD_OUT, &di);
+        if (tamd_stage_open(&st, space)) return -1;
         struct stack_call call = { stack, n, da, db, dz, NULL, di, 0 };
         const int rc = stack_rounds(&call, message, size);
         if (rc != 0) return rc;
-        if (tamd_stage_fetch(&st, elevation, nb, dz) ||
-            tamd_stage_fetch(&st, inside, n * sizeof(int), di))
-                return -1;
-        return tamd_stage_end(&st) ? -1 : 0;
+        return tamd_stage_close(&st) ? -1 : 0;
 }
 
 enum turtle_return turtle_stack_elevation_n(struct turtle_stack * stack, long n,
@@ -851,21 +848,19 @@ static int stack_gradient_n(struct turtle_stack * stack, long n, const double * 
     const double * longitude, double * glat, double * glon, int * inside, int space,
     char * message, size_t size)
 {
-        struct tamd_stage st;
+        struct tamd_stage st = { 0 };
         void *da, *db, *dga, *dgb, *di;
         const size_t nb = (size_t)n * sizeof(double);
-        if (tamd_stage_begin(&st, space, 4 * nb + n * sizeof(int))) return -1;
-        if (tamd_stage_in(&st, latitude, nb, &da) || tamd_stage_in(&st, longitude, nb, &db) ||
-            tamd_stage_in(&st, glat, nb, &dga) || tamd_stage_in(&st, glon, nb, &dgb) ||
-            tamd_stage_out(&st, inside, n * sizeof(int), &di))
-                return -1;
+        tamd_stage_add(&st, latitude, nb, TAMD_IN, &da);
+        tamd_stage_add(&st, longitude, nb, TAMD_IN, &db);
+        tamd_stage_add(&st, glat, nb, TAMD_INOUT, &dga);
+        tamd_stage_add(&st, glon, nb, TAMD_INOUT, &dgb);
+        tamd_stage_add(&st, inside, n * sizeof(int), TAMD_OUT, &di);
+        if (tamd_stage_open(&st, space)) return -1;
         struct stack_call call = { stack, n, da, db, dga, dgb, di, 1 };
         const int rc = stack_rounds(&call, message, size);
         if (rc != 0) return rc;
-        if (tamd_stage_fetch(&st, glat, nb, dga) || tamd_stage_fetch(&st, glon, nb, dgb) ||
-            tamd_stage_fetch(&st, inside, n * sizeof(int), di))
-                return -1;
-        return tamd_stage_end(&st) ? -1 : 0;
+        return tamd_stage_close(&st) ? -1 : 0;
 }
 
 enum turtle_return turtle_stack_gradient_n(struct turtle_stack * stack, long n,

@@ -507,6 +507,15 @@ static int stepper_flatten_locked(struct turtle_stepper * s, char * message, siz
         return dev_fail ? -1 : 0;
 }
 
+/* What stepper_rounds, stepper_resident or tamd_stepper_flatten returned (not 0), raised: a
+ * device failure (< 0, or TURTLE_RETURN_LIBRARY_ERROR) with the device's text, any other code
+ * with the text they left in stepper->message */
+#define RAISE_ROUNDS(stepper, rc)                                              \
+        ((((rc) < 0) || ((rc) == TURTLE_RETURN_LIBRARY_ERROR)) ?               \
+                TAMD_RAISE_DEVICE() :                                          \
+                TAMD_RAISE((enum turtle_return)(rc), "%s", (stepper)->message))
+#define FLATTEN(stepper) tamd_stepper_flatten((stepper), (stepper)->message, sizeof((stepper)->message))
+
 /* ---- batch calls over paged stacks (paging.c) --------------------------- */
 
 static int stepper_is_paged(const struct turtle_stepper * s)
@@ -538,14 +547,15 @@ static int stepper_page_in(struct turtle_stepper * s, const unsigned * wanted,
 }
 
 /* Runs `launch` (the kernels of one round) until nothing is listed any more.
- * Returns an enum turtle_return; TURTLE_RETURN_LIBRARY_ERROR: device failure
- * (message empty) */
+ * Returns an enum turtle_return; TURTLE_RETURN_LIBRARY_ERROR: device failure; any
+ * other failure has its text in stepper->message (RAISE_ROUNDS raises either) */
 typedef int stepper_round_t(struct turtle_stepper * stepper, struct tamd_paging pg, int round,
     void * args);
 
-static int stepper_rounds(struct turtle_stepper * stepper, long n, stepper_round_t * launch,
-    void * args, char * message, size_t size)
+static int stepper_rounds(struct turtle_stepper * stepper, long n, stepper_round_t * launch, void * args)
 {
+        char * const message = stepper->message;
+        const size_t size = sizeof(stepper->message);
         struct tamd_pager pager;
         memset(&pager, 0, sizeof(pager));
         message[0] = 0;
@@ -618,6 +628,20 @@ static int stepper_rounds(struct turtle_stepper * stepper, long n, stepper_round
         return rc;
 }
 
+/* Every tile resident: the whole call in ONE launch (no paging: pg.first_id -1), over tables
+ * made current with the geometry held in use until the launch is queued.  Returns as
+ * stepper_rounds.  (What turtle_amd_stepper_rounds reports is the caller's to set: scatter_n
+ * leaves it as its last rounds did.) */
+static int stepper_resident(struct turtle_stepper * stepper, stepper_round_t * launch, void * args)
+{
+        const struct tamd_paging none = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, -1 };
+        tamd_geometry_use_begin();
+        int rc = FLATTEN(stepper);
+        if ((rc < 0) || ((rc == 0) && launch(stepper, none, 0, args))) rc = TURTLE_RETURN_LIBRARY_ERROR;
+        tamd_geometry_use_end();
+        return rc;
+}
+
 /* ---- a device view: the geometry lent to the caller's own kernel ------------- */
 
 void turtle_amd_view_layout(int * version, size_t * size)
@@ -638,7 +662,6 @@ enum turtle_return turtle_amd_stepper_view_acquire(struct turtle_stepper * stepp
         if (stepper->view_out) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "the stepper's view is out already");
         if (tamd_dev_init()) return TAMD_RAISE_DEVICE();
         /* every tile of every stack in memory (turtle_stack_load), before the span begins */
-        char message[4200];
         int i;
         for (i = 0; i < stepper->n_data; i++) {
                 if (stepper->data[i].kind != TAMD_STACK) continue;
@@ -653,13 +676,12 @@ enum turtle_return turtle_amd_stepper_view_acquire(struct turtle_stepper * stepp
                 if (rc != TURTLE_RETURN_SUCCESS) return rc;
         }
         tamd_geometry_use_begin();
-        int rc = tamd_stepper_flatten(stepper, message, sizeof(message));
+        int rc = FLATTEN(stepper);
         int paged = 0;
         if (rc == 0) paged = stepper_is_paged(stepper); /* (a tile another thread took meanwhile) */
         if ((rc != 0) || paged) {
                 tamd_geometry_use_end();
-                if (rc < 0) return TAMD_RAISE_DEVICE();
-                if (rc > 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
+                if (rc != 0) return RAISE_ROUNDS(stepper, rc);
                 return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "a tile left its stack while the view was made: try again");
         }
         struct turtle_amd_view out;
@@ -685,14 +707,6 @@ enum turtle_return turtle_amd_stepper_view_release(struct turtle_stepper * stepp
         tamd_geometry_use_end();
         return TURTLE_RETURN_SUCCESS;
 }
-
-#define FLATTEN_OR_RETURN(stepper)                                             \
-        do {                                                                   \
-                char message_[4200];                                           \
-                const int rc_ = tamd_stepper_flatten((stepper), message_, sizeof(message_)); \
-                if (rc_ < 0) return TAMD_RAISE_DEVICE();                       \
-                if (rc_ > 0) return TAMD_RAISE((enum turtle_return)rc_, "%s", message_); \
-        } while (0)
 
 /* ---- batch entry points --------------------------------------------------- */
 
@@ -720,23 +734,18 @@ enum turtle_return turtle_stepper_position_n(struct turtle_stepper * stepper, lo
                 return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "no valid data");
         if ((position == NULL) || (data_index == NULL))
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
-        struct tamd_stage st;
+        struct tamd_stage st = { 0 };
         struct position_args args = { n, NULL, NULL, NULL, layer_index, NULL, NULL };
         const size_t nb = (size_t)n * sizeof(double);
-        if (tamd_stage_begin(&st, space, 6 * nb + n * sizeof(int)) ||
-            tamd_stage_in(&st, latitude, nb, &args.lat) ||
-            tamd_stage_in(&st, longitude, nb, &args.lon) ||
-            tamd_stage_in(&st, height, nb, &args.height) ||
-            tamd_stage_in(&st, position, 3 * nb, &args.pos) || /* untouched rows keep their value */
-            tamd_stage_out(&st, data_index, n * sizeof(int), &args.index))
-                return TAMD_RAISE_DEVICE();
-        char message[4200];
-        const int rc = stepper_rounds(stepper, n, &position_round, &args, message, sizeof(message));
-        if (rc == TURTLE_RETURN_LIBRARY_ERROR) return TAMD_RAISE_DEVICE();
-        if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
-        if (tamd_stage_fetch(&st, position, 3 * nb, args.pos) ||
-            tamd_stage_fetch(&st, data_index, n * sizeof(int), args.index) || tamd_stage_end(&st))
-                return TAMD_RAISE_DEVICE();
+        tamd_stage_add(&st, latitude, nb, TAMD_IN, &args.lat);
+        tamd_stage_add(&st, longitude, nb, TAMD_IN, &args.lon);
+        tamd_stage_add(&st, height, nb, TAMD_IN, &args.height);
+        tamd_stage_add(&st, position, 3 * nb, TAMD_INOUT, &args.pos); /* untouched rows keep their value */
+        tamd_stage_add(&st, data_index, n * sizeof(int), TAMD_OUT, &args.index);
+        if (tamd_stage_open(&st, space)) return TAMD_RAISE_DEVICE();
+        const int rc = stepper_rounds(stepper, n, &position_round, &args);
+        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
+        if (tamd_stage_close(&st)) return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
 }
 
@@ -806,47 +815,29 @@ static enum turtle_return step_n(struct tamd_error * error, struct turtle_steppe
             ((altitude == NULL) || (elevation == NULL)))
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS,
                     "TURTLE_AMD_STEP_RESUME needs altitude, elevation and index");
-        struct tamd_stage st;
-        void *dp, *dd, *dla, *dlo, *dal, *del, *dst, *dix;
+        struct tamd_stage st = { 0 };
+        struct step_args args = { n, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, flags, 0 };
         const size_t nb = (size_t)n * sizeof(double);
-        const int resume = (flags & TURTLE_AMD_STEP_RESUME) != 0;
-        if (tamd_stage_begin(&st, space, 12 * nb + 2 * n * sizeof(int)) ||
-            tamd_stage_in(&st, position, 3 * nb, &dp) ||
-            tamd_stage_in(&st, direction, 3 * nb, &dd))
-                return TAMD_RAISE_DEVICE();
-        int bad = 0;
-        if (resume) {
-                bad |= tamd_stage_in(&st, latitude, nb, &dla);
-                bad |= tamd_stage_in(&st, longitude, nb, &dlo);
-                bad |= tamd_stage_in(&st, altitude, nb, &dal);
-                bad |= tamd_stage_in(&st, elevation, 2 * nb, &del);
-                bad |= tamd_stage_in(&st, index, 2 * n * sizeof(int), &dix);
-        } else {
-                bad |= tamd_stage_out(&st, latitude, nb, &dla);
-                bad |= tamd_stage_out(&st, longitude, nb, &dlo);
-                bad |= tamd_stage_out(&st, altitude, nb, &dal);
-                bad |= tamd_stage_out(&st, elevation, 2 * nb, &del);
-                bad |= tamd_stage_out(&st, index, 2 * n * sizeof(int), &dix);
-        }
-        bad |= tamd_stage_out(&st, step, nb, &dst);
+        /* a step moves the position; a sample leaves it.  The sample is the call's result, and
+         * what a resumed call starts from as well */
+        const int sample = (flags & TURTLE_AMD_STEP_RESUME) ? TAMD_INOUT : TAMD_OUT;
+        tamd_stage_add(&st, position, 3 * nb, (direction != NULL) ? TAMD_INOUT : TAMD_IN, &args.pos);
+        tamd_stage_add(&st, direction, 3 * nb, TAMD_IN, &args.dir);
+        tamd_stage_add(&st, latitude, nb, sample, &args.lat);
+        tamd_stage_add(&st, longitude, nb, sample, &args.lon);
+        tamd_stage_add(&st, altitude, nb, sample, &args.alt);
+        tamd_stage_add(&st, elevation, 2 * nb, sample, &args.elev);
+        tamd_stage_add(&st, index, 2 * n * sizeof(int), sample, &args.index);
+        tamd_stage_add(&st, step, nb, TAMD_OUT, &args.step);
+        if (tamd_stage_open(&st, space)) return TAMD_RAISE_DEVICE();
         /* with a direction: two passes, the second for the rays that crossed a
          * boundary (a single step bisects in place: nothing to pack) */
-        const int listed = (direction != NULL) && (n > 1) && (tamd_stepper_scratch(stepper, n) == 0);
-        if ((direction != NULL) && (n > 1) && !listed && (stepper->parked_capacity < 0)) bad = 1;
-        if (bad) return TAMD_RAISE_DEVICE();
-        struct step_args args = { n, dp, dd, dla, dlo, dal, del, dst, dix, flags, listed };
-        char message[4200];
-        const int rc = stepper_rounds(stepper, n, &step_round, &args, message, sizeof(message));
-        if (rc == TURTLE_RETURN_LIBRARY_ERROR) return TAMD_RAISE_DEVICE();
-        if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
-        if (((direction != NULL) && tamd_stage_fetch(&st, position, 3 * nb, dp)) ||
-            tamd_stage_fetch(&st, latitude, nb, dla) ||
-            tamd_stage_fetch(&st, longitude, nb, dlo) ||
-            tamd_stage_fetch(&st, altitude, nb, dal) ||
-            tamd_stage_fetch(&st, elevation, 2 * nb, del) ||
-            tamd_stage_fetch(&st, step, nb, dst) ||
-            tamd_stage_fetch(&st, index, 2 * n * sizeof(int), dix) || tamd_stage_end(&st))
+        args.listed = (direction != NULL) && (n > 1) && (tamd_stepper_scratch(stepper, n) == 0);
+        if ((direction != NULL) && (n > 1) && !args.listed && (stepper->parked_capacity < 0))
                 return TAMD_RAISE_DEVICE();
+        const int rc = stepper_rounds(stepper, n, &step_round, &args);
+        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
+        if (tamd_stage_close(&st)) return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
 }
 
@@ -857,6 +848,7 @@ struct walk_args {
         void *pos, *alt, *elev, *index, *length, *steps;
         unsigned long long seed, stream;
         long first;
+        int first_step, n_steps;
 };
 
 static int walk_round(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
@@ -876,6 +868,14 @@ static int walk_start_round(struct turtle_stepper * stepper, struct tamd_paging 
             a->index, 0, pg);
 }
 
+static int walk_resident(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
+{
+        struct walk_args * a = p;
+        (void)pg, (void)round;
+        return tamd_k_walk(stepper->view, a->n, a->pos, a->alt, a->elev, a->index, a->seed, a->first,
+            a->first_step, a->n_steps, a->length, a->steps, stepper->d_stats, stepper->d_stats + 4);
+}
+
 enum turtle_return turtle_stepper_scatter_n(struct turtle_stepper * stepper, long n,
     double * position, unsigned long long seed, long first_ray, int first_step, int n_steps,
     double * altitude, double * elevation, int * index, double * length, int * steps, int flags,
@@ -892,35 +892,25 @@ enum turtle_return turtle_stepper_scatter_n(struct turtle_stepper * stepper, lon
                 if (stepper->parked_capacity < 0) return TAMD_RAISE_DEVICE();
                 return TAMD_RAISE(TURTLE_RETURN_MEMORY_ERROR, "batch too large");
         }
-        struct tamd_stage st;
-        struct walk_args a = { n, NULL, NULL, NULL, NULL, NULL, NULL, seed, 0, first_ray };
+        struct tamd_stage st = { 0 };
+        struct walk_args a = { n, NULL, NULL, NULL, NULL, NULL, NULL, seed, 0, first_ray, first_step, n_steps };
         const size_t nb = (size_t)n * sizeof(double);
         const int start = (flags & TURTLE_AMD_SCATTER_START) != 0;
-        int bad = tamd_stage_begin(&st, space, 7 * nb + 3 * n * sizeof(int)) ||
-            tamd_stage_in(&st, position, 3 * nb, &a.pos);
-        if (!bad && start)
-                bad = tamd_stage_out(&st, altitude, nb, &a.alt) ||
-                    tamd_stage_out(&st, elevation, 2 * nb, &a.elev) ||
-                    tamd_stage_out(&st, index, 2 * n * sizeof(int), &a.index) ||
-                    tamd_stage_out(&st, length, nb, &a.length) ||
-                    tamd_stage_out(&st, steps, n * sizeof(int), &a.steps);
-        else if (!bad)
-                bad = tamd_stage_in(&st, altitude, nb, &a.alt) ||
-                    tamd_stage_in(&st, elevation, 2 * nb, &a.elev) ||
-                    tamd_stage_in(&st, index, 2 * n * sizeof(int), &a.index) ||
-                    tamd_stage_in(&st, length, nb, &a.length) ||
-                    tamd_stage_in(&st, steps, n * sizeof(int), &a.steps);
-        if (bad) return TAMD_RAISE_DEVICE();
-        char message[4200];
+        const int state = start ? TAMD_OUT : TAMD_INOUT; /* made here, or carried from call to call */
+        tamd_stage_add(&st, position, 3 * nb, TAMD_INOUT, &a.pos);
+        tamd_stage_add(&st, altitude, nb, state, &a.alt);
+        tamd_stage_add(&st, elevation, 2 * nb, state, &a.elev);
+        tamd_stage_add(&st, index, 2 * n * sizeof(int), state, &a.index);
+        tamd_stage_add(&st, length, nb, state, &a.length);
+        tamd_stage_add(&st, steps, n * sizeof(int), state, &a.steps);
+        if (tamd_stage_open(&st, space)) return TAMD_RAISE_DEVICE();
         int rc = 0, k;
         if (start) {
-                rc = stepper_rounds(stepper, n, &walk_start_round, &a, message, sizeof(message));
+                rc = stepper_rounds(stepper, n, &walk_start_round, &a);
                 if ((rc == 0) && (tamd_dev_zero(a.length, nb) || tamd_dev_zero(a.steps, n * sizeof(int))))
                         rc = TURTLE_RETURN_LIBRARY_ERROR;
-        } else if (stepper->d_stats == NULL) {
-                rc = tamd_stepper_flatten(stepper, message, sizeof(message));
-                if (rc < 0) rc = TURTLE_RETURN_LIBRARY_ERROR;
-        }
+        } else if (stepper->d_stats == NULL)
+                rc = FLATTEN(stepper);
         /* the counters are those of THIS call (turtle_stepper_trace_stats), whatever the
          * stepper's last batch left there */
         if ((rc == 0) && tamd_dev_zero(stepper->d_stats, 4 * sizeof(*stepper->d_stats)))
@@ -934,28 +924,15 @@ enum turtle_return turtle_stepper_scatter_n(struct turtle_stepper * stepper, lon
                 by_steps = ((env != NULL) && (strcmp(env, "steps") == 0)) ? 1 : 0;
         }
         if ((rc == 0) && !by_steps && !stepper_is_paged(stepper) && (n_steps > 0)) {
-                tamd_geometry_use_begin();
-                rc = tamd_stepper_flatten(stepper, message, sizeof(message));
-                if (rc < 0) rc = TURTLE_RETURN_LIBRARY_ERROR;
-                if ((rc == 0) && tamd_k_walk(stepper->view, n, a.pos, a.alt, a.elev, a.index, seed,
-                        first_ray, first_step, n_steps, a.length, a.steps, stepper->d_stats,
-                        stepper->d_stats + 4))
-                        rc = TURTLE_RETURN_LIBRARY_ERROR;
-                tamd_geometry_use_end();
+                rc = stepper_resident(stepper, &walk_resident, &a);
                 n_steps = 0;
         }
         for (k = 0; (rc == 0) && (k < n_steps); k++) {
                 a.stream = (unsigned long long)(first_step + k);
-                rc = stepper_rounds(stepper, n, &walk_round, &a, message, sizeof(message));
+                rc = stepper_rounds(stepper, n, &walk_round, &a);
         }
-        if (rc == TURTLE_RETURN_LIBRARY_ERROR) return TAMD_RAISE_DEVICE();
-        if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
-        if (tamd_stage_fetch(&st, position, 3 * nb, a.pos) || tamd_stage_fetch(&st, altitude, nb, a.alt) ||
-            tamd_stage_fetch(&st, elevation, 2 * nb, a.elev) ||
-            tamd_stage_fetch(&st, index, 2 * n * sizeof(int), a.index) ||
-            tamd_stage_fetch(&st, length, nb, a.length) ||
-            tamd_stage_fetch(&st, steps, n * sizeof(int), a.steps) || tamd_stage_end(&st))
-                return TAMD_RAISE_DEVICE();
+        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
+        if (tamd_stage_close(&st)) return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
 }
 
@@ -1008,17 +985,15 @@ enum turtle_return turtle_stepper_trace_n(struct turtle_stepper * stepper, long 
         struct trace_args args = { n, NULL, NULL, NULL, NULL, NULL, max_steps, flags, 0 };
         args.scratch = (tamd_stepper_scratch(stepper, n) == 0);
         if (!args.scratch && (stepper->parked_capacity < 0)) return TAMD_RAISE_DEVICE();
-        struct tamd_stage st;
+        struct tamd_stage st = { 0 };
         const size_t nb = (size_t)n * sizeof(double);
-        if (tamd_stage_begin(&st, space, 7 * nb + 3 * n * sizeof(int)) ||
-            tamd_stage_in(&st, position, 3 * nb, &args.pos) ||
-            tamd_stage_in(&st, direction, 3 * nb, &args.dir) ||
-            ((flags & TURTLE_AMD_TRACE_RESUME) ?
-                    tamd_stage_in(&st, index, 2 * n * sizeof(int), &args.index) :
-                    tamd_stage_out(&st, index, 2 * n * sizeof(int), &args.index)) ||
-            tamd_stage_out(&st, length, nb, &args.length) ||
-            tamd_stage_out(&st, n_steps, n * sizeof(int), &args.n_steps))
-                return TAMD_RAISE_DEVICE();
+        tamd_stage_add(&st, position, 3 * nb, TAMD_INOUT, &args.pos);
+        tamd_stage_add(&st, direction, 3 * nb, TAMD_IN, &args.dir);
+        tamd_stage_add(&st, index, 2 * n * sizeof(int),
+            (flags & TURTLE_AMD_TRACE_RESUME) ? TAMD_INOUT : TAMD_OUT, &args.index);
+        tamd_stage_add(&st, length, nb, TAMD_OUT, &args.length);
+        tamd_stage_add(&st, n_steps, n * sizeof(int), TAMD_OUT, &args.n_steps);
+        if (tamd_stage_open(&st, space)) return TAMD_RAISE_DEVICE();
         /* a ray that waits for a tile keeps its path length and step count in
          * these arrays, and so does a ray handed from pass to pass: they exist
          * even if the caller has none -- which outputs a caller asks for changes
@@ -1026,19 +1001,13 @@ enum turtle_return turtle_stepper_trace_n(struct turtle_stepper * stepper, long 
         if (stepper_is_paged(stepper) && !args.scratch)
                 return TAMD_RAISE(TURTLE_RETURN_MEMORY_ERROR,
                     "a batch this large cannot run over stacks with tiles left to page in");
-        if (args.scratch && (n > 0)) {
+        if (args.scratch && (n > 0)) { /* (in place of the NULL of an array that is not brought back) */
                 if (args.length == NULL) args.length = stepper->d_scratch_ds + 2 * n;
                 if (args.n_steps == NULL) args.n_steps = stepper->d_parked + 3 * n;
         }
-        char message[4200];
-        const int rc = stepper_rounds(stepper, n, &trace_round, &args, message, sizeof(message));
-        if (rc == TURTLE_RETURN_LIBRARY_ERROR) return TAMD_RAISE_DEVICE();
-        if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
-        if (tamd_stage_fetch(&st, position, 3 * nb, args.pos) ||
-            tamd_stage_fetch(&st, index, 2 * n * sizeof(int), args.index) ||
-            tamd_stage_fetch(&st, length, nb, args.length) ||
-            tamd_stage_fetch(&st, n_steps, n * sizeof(int), args.n_steps) || tamd_stage_end(&st))
-                return TAMD_RAISE_DEVICE();
+        const int rc = stepper_rounds(stepper, n, &trace_round, &args);
+        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
+        if (tamd_stage_close(&st)) return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
 }
 
@@ -1079,7 +1048,7 @@ static void * traverse_piece(char * block, size_t * used, size_t bytes)
  * same values as k_traverse in STRICT: the same bits. */
 static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos, const double * dir,
     double ceiling, int max_steps, int * index, double * length, int * n_steps, int * n_cross,
-    const struct tamd_crossings * rec, char * message, size_t size)
+    const struct tamd_crossings * rec)
 {
         /* the sample state between generations, the counts the caller may not want and, recording
          * crossings, the running totals */
@@ -1100,7 +1069,7 @@ static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos,
         if (n_steps == NULL) n_steps = own;
         if (n_cross == NULL) n_cross = own + n;
         /* counters: [0, 4) k_traverse_gen's; the step kernels' stats are in d_stats[8, 12) */
-        int rc = stepper_rounds(stepper, n, &traverse_start_round, &a, message, size);
+        int rc = stepper_rounds(stepper, n, &traverse_start_round, &a);
         int rounds = stepper->last_rounds; /* (turtle_amd_stepper_rounds: the most a generation took) */
         if ((rc == 0) && (tamd_dev_zero(counters, 4 * sizeof(*counters)) ||
                              tamd_dev_zero(stepper->d_stats + 8, 4 * sizeof(*stepper->d_stats)) ||
@@ -1119,7 +1088,7 @@ static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos,
                         rc = TURTLE_RETURN_LIBRARY_ERROR;
                         break;
                 }
-                rc = stepper_rounds(stepper, n, &traverse_round, &a, message, size);
+                rc = stepper_rounds(stepper, n, &traverse_round, &a);
                 if (stepper->last_rounds > rounds) rounds = stepper->last_rounds;
                 if ((rc == 0) && (total != NULL) &&
                     tamd_k_crossings_gen(n, a.pos, a.step, a.live, medium, n_cross, total, *rec))
@@ -1142,6 +1111,22 @@ static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos,
         return rc;
 }
 
+struct sight_args {
+        long n;
+        void *pos, *dir, *index, *length, *n_steps, *n_cross, *point, *distance, *media;
+        double ceiling;
+        int max_steps;
+        const struct tamd_crossings * rec; /* the three arrays above, or NULL */
+};
+
+static int sight_resident(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
+{
+        struct sight_args * a = p;
+        (void)pg, (void)round;
+        return tamd_k_traverse(stepper->view, a->n, a->pos, a->dir, a->ceiling, a->max_steps, a->index,
+            a->length, a->n_steps, a->n_cross, a->rec, stepper->d_stats, stepper->d_stats + 4);
+}
+
 /* turtle_stepper_traverse_n and, rec != NULL (the caller's arrays), turtle_stepper_crossings_n */
 static enum turtle_return traverse_n(struct tamd_error * error, struct turtle_stepper * stepper, long n,
     double * position, const double * direction, double altitude_max, int max_steps, int * index,
@@ -1152,59 +1137,48 @@ static enum turtle_return traverse_n(struct tamd_error * error, struct turtle_st
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
         if (max_steps < 0) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid input parameter(s)");
         if (n <= 0) return TURTLE_RETURN_SUCCESS;
-        char message[4200];
-        int rc = tamd_stepper_flatten(stepper, message, sizeof(message));
-        if (rc < 0) return TAMD_RAISE_DEVICE();
-        if (rc > 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
+        int rc = FLATTEN(stepper);
+        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
         const int paged = stepper_is_paged(stepper);
         if (paged && (tamd_stepper_scratch(stepper, n) != 0)) {
                 if (stepper->parked_capacity < 0) return TAMD_RAISE_DEVICE();
                 return TAMD_RAISE(TURTLE_RETURN_MEMORY_ERROR, "batch too large");
         }
         const long media = stepper->n_layers + 1;
-        struct tamd_stage st;
-        void *dp, *dd, *dix, *dlen, *dst, *dcr, *dpt = NULL, *ddi = NULL, *dme = NULL;
+        struct tamd_stage st = { 0 };
+        struct sight_args a = { n, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, altitude_max,
+                max_steps, NULL };
         const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int);
         const size_t slots = (rec != NULL) ? (size_t)rec->capacity : 0; /* (of n rays each) */
-        if (tamd_stage_begin(&st, space, (6 + media + 4 * slots) * nb + (4 + 2 * slots) * ni) ||
-            tamd_stage_in(&st, position, 3 * nb, &dp) || tamd_stage_in(&st, direction, 3 * nb, &dd) ||
-            tamd_stage_out(&st, index, 2 * ni, &dix) || tamd_stage_out(&st, length, media * nb, &dlen) ||
-            tamd_stage_out(&st, n_steps, ni, &dst) || tamd_stage_out(&st, n_crossings, ni, &dcr) ||
-            ((rec != NULL) && (tamd_stage_out(&st, rec->point, 3 * slots * nb, &dpt) ||
-                                  tamd_stage_out(&st, rec->distance, slots * nb, &ddi) ||
-                                  tamd_stage_out(&st, rec->media, 2 * slots * ni, &dme))))
-                return TAMD_RAISE_DEVICE();
+        tamd_stage_add(&st, position, 3 * nb, TAMD_INOUT, &a.pos);
+        tamd_stage_add(&st, direction, 3 * nb, TAMD_IN, &a.dir);
+        tamd_stage_add(&st, index, 2 * ni, TAMD_OUT, &a.index);
+        tamd_stage_add(&st, length, media * nb, TAMD_OUT, &a.length);
+        tamd_stage_add(&st, n_steps, ni, TAMD_OUT, &a.n_steps);
+        tamd_stage_add(&st, n_crossings, ni, TAMD_OUT, &a.n_cross);
+        if (rec != NULL) {
+                tamd_stage_add(&st, rec->point, 3 * slots * nb, TAMD_OUT, &a.point);
+                tamd_stage_add(&st, rec->distance, slots * nb, TAMD_OUT, &a.distance);
+                tamd_stage_add(&st, rec->media, 2 * slots * ni, TAMD_OUT, &a.media);
+        }
+        if (tamd_stage_open(&st, space)) return TAMD_RAISE_DEVICE();
+        const struct tamd_crossings drec = { a.point, a.distance, a.media, (int)slots };
+        if (rec != NULL) a.rec = &drec;
         /* the sums are added to where they stand: they start from zero; and the slots past a ray's
          * crossings are zero (media {0, 0}) */
-        if ((dlen != NULL) && tamd_dev_zero(dlen, media * nb)) return TAMD_RAISE_DEVICE();
-        if ((slots > 0) && (((dpt != NULL) && tamd_dev_zero(dpt, 3 * slots * nb)) ||
-                               ((ddi != NULL) && tamd_dev_zero(ddi, slots * nb)) ||
-                               ((dme != NULL) && tamd_dev_zero(dme, 2 * slots * ni))))
+        if ((a.length != NULL) && tamd_dev_zero(a.length, media * nb)) return TAMD_RAISE_DEVICE();
+        if ((slots > 0) && (((a.point != NULL) && tamd_dev_zero(a.point, 3 * slots * nb)) ||
+                               ((a.distance != NULL) && tamd_dev_zero(a.distance, slots * nb)) ||
+                               ((a.media != NULL) && tamd_dev_zero(a.media, 2 * slots * ni))))
                 return TAMD_RAISE_DEVICE();
-        const struct tamd_crossings drec = { dpt, ddi, dme, (int)slots };
         if (!paged) { /* every tile resident: the whole traverse in one launch */
-                tamd_geometry_use_begin();
-                rc = tamd_stepper_flatten(stepper, message, sizeof(message));
-                if (rc < 0) rc = TURTLE_RETURN_LIBRARY_ERROR;
-                if ((rc == 0) && tamd_k_traverse(stepper->view, n, dp, dd, altitude_max, max_steps, dix,
-                                     dlen, dst, dcr, (rec != NULL) ? &drec : NULL, stepper->d_stats,
-                                     stepper->d_stats + 4))
-                        rc = TURTLE_RETURN_LIBRARY_ERROR;
-                tamd_geometry_use_end();
+                rc = stepper_resident(stepper, &sight_resident, &a);
                 stepper->last_rounds = 1;
         } else
-                rc = traverse_paged(stepper, n, dp, dd, altitude_max, max_steps, dix, dlen, dst, dcr,
-                    (rec != NULL) ? &drec : NULL, message, sizeof(message));
-        if (rc == TURTLE_RETURN_LIBRARY_ERROR) return TAMD_RAISE_DEVICE();
-        if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
-        if (tamd_stage_fetch(&st, position, 3 * nb, dp) || tamd_stage_fetch(&st, index, 2 * ni, dix) ||
-            tamd_stage_fetch(&st, length, media * nb, dlen) || tamd_stage_fetch(&st, n_steps, ni, dst) ||
-            tamd_stage_fetch(&st, n_crossings, ni, dcr) ||
-            ((rec != NULL) && (tamd_stage_fetch(&st, rec->point, 3 * slots * nb, dpt) ||
-                                  tamd_stage_fetch(&st, rec->distance, slots * nb, ddi) ||
-                                  tamd_stage_fetch(&st, rec->media, 2 * slots * ni, dme))) ||
-            tamd_stage_end(&st))
-                return TAMD_RAISE_DEVICE();
+                rc = traverse_paged(stepper, n, a.pos, a.dir, altitude_max, max_steps, a.index, a.length,
+                    a.n_steps, a.n_cross, a.rec);
+        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
+        if (tamd_stage_close(&st)) return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
 }
 
@@ -1253,11 +1227,10 @@ enum turtle_return turtle_stepper_step(struct turtle_stepper * stepper, double *
 {
         TAMD_ERROR_INIT(&turtle_stepper_step);
         if (tamd_scalar_on_host() && tamd_h_stepper_takes(stepper)) { /* (the caller's option: scalar.c) */
-                char message[4200];
                 const int rc = tamd_h_stepper_step(stepper, position, direction, latitude, longitude,
-                    altitude, elevation, step, index, message, sizeof(message));
+                    altitude, elevation, step, index, stepper->message, sizeof(stepper->message));
                 if (rc == TURTLE_RETURN_DOMAIN_ERROR) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "no valid data");
-                if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
+                if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", stepper->message);
                 return TURTLE_RETURN_SUCCESS;
         }
         int idx[2] = { -1, -1 };
@@ -1280,10 +1253,9 @@ enum turtle_return turtle_stepper_position(struct turtle_stepper * stepper, doub
                 return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "no valid data");
         int di = -1;
         if (tamd_scalar_on_host() && tamd_h_stepper_takes(stepper)) { /* (the caller's option: scalar.c) */
-                char message[4200];
                 const int rc = tamd_h_stepper_position(stepper, latitude, longitude, height, layer_index,
-                    position, &di, message, sizeof(message));
-                if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", message);
+                    position, &di, stepper->message, sizeof(stepper->message));
+                if (rc != 0) return TAMD_RAISE((enum turtle_return)rc, "%s", stepper->message);
                 if (data_index != NULL)
                         *data_index = di;
                 else if (di < 0)
