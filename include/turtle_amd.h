@@ -118,14 +118,20 @@ TURTLE_API enum turtle_return turtle_projection_unproject(
  * `projection` is NULL for a geodetic grid (x = longitude, y = latitude) or a
  * projection name; under a stepper a projected map is looked up at the
  * projected coordinates [impl stepper.c:65-83, :243-248].
- * turtle_map_load reads .hgt tiles [impl io/hgt.c:45-151] and uncompressed,
- * stripped GeoTIFF-16 .tif files [impl io/geotiff16.c:165-258] with a native
- * reader (no libtiff), and the reference's own .png map format (16-bit
+ * turtle_map_load reads .hgt tiles [impl io/hgt.c:45-151] and GeoTIFF-16
+ * .tif files [impl io/geotiff16.c:165-258] with a native reader (no libtiff):
+ * classic TIFF in strips, either byte order, one 16-bit sample a pixel,
+ * Compression 1 (none), 5 (LZW), 8 or 32946 (Deflate) or 32773 (PackBits),
+ * with LZW and Deflate also Predictor 2 (horizontal differencing) -- which is
+ * how ASTER GDEM, SRTM and GDAL exports ship; and the reference's own .png map format (16-bit
  * greyscale + JSON "topography" header, incl. its projection) [impl
  * io/png16.c:183-448] with a native reader (zlib's inflate only), and the
  * text formats .grd / .asc [impl io/grd.c, io/asc.c]; other
- * extensions return TURTLE_RETURN_BAD_EXTENSION, compressed or tiled TIFFs and
- * non-16-bit or interlaced PNGs TURTLE_RETURN_BAD_FORMAT. */
+ * extensions return TURTLE_RETURN_BAD_EXTENSION.  TURTLE_RETURN_BAD_FORMAT:
+ * tiled TIFFs, BigTIFF, any other compression (JPEG, CCITT, LZMA, ZSTD ...)
+ * or predictor, FillOrder 2, a compressed file without StripByteCounts or with
+ * a strip beyond the end of the file, a strip that does not decode to exactly
+ * its rows ("missing data"); non-16-bit or interlaced PNGs. */
 TURTLE_API enum turtle_return turtle_map_create(struct turtle_map ** map,
     const struct turtle_map_info * info, const char * projection);
 TURTLE_API void turtle_map_destroy(struct turtle_map ** map);

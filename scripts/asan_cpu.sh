@@ -17,4 +17,4 @@ cd $ROOT
 python -m pytest tests/test_stage_host.py -x -q
 LD_PRELOAD="$(gcc -print-file-name=libasan.so) $(gcc -print-file-name=libubsan.so)" ASAN_OPTIONS=detect_leaks=0 \
   UBSAN_OPTIONS=print_stacktrace=1 TURTLE_AMD_LIBRARY=/tmp/asan/libturtle_amd.so \
-  python -m pytest tests/test_host_scalar.py tests/test_host_logic.py tests/test_cabi_symbols.py -x -q
+  python -m pytest tests/test_host_scalar.py tests/test_host_logic.py tests/test_cabi_symbols.py tests/test_tiff_compressed.py -x -q

@@ -49,6 +49,8 @@ struct turtle_map {
         int is_signed;        /* int16 codecs (hgt): z = (int16)v */
         struct turtle_projection projection; /* type < 0: geodetic */
         struct turtle_stack * stack; /* owner, or NULL */
+        int rows_together;    /* set by a probe: rows of the file that only decode together (the strips
+                               * of a compressed GeoTIFF), 0 where any row is read on its own */
 
         uint16_t * nodes;     /* host copy: native endian, rows south->north -- or NULL for a
                                * tile that came back from a staging buffer (stage_tile): the

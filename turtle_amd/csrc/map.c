@@ -142,7 +142,7 @@ void turtle_map_destroy(struct turtle_map ** map)
 }
 
 /* Extension dispatch [ref src/turtle/io.c:60-104]: the reference's five
- * formats -- hgt, GeoTIFF-16 (uncompressed strips), PNG-16 maps, grd, asc. */
+ * formats -- hgt, GeoTIFF-16 (strips; see tiff.c), PNG-16 maps, grd, asc. */
 int tamd_codec_for(const char * path, int (**probe)(const char *, struct turtle_map *),
     int (**read)(const char *, struct turtle_map *))
 {
@@ -212,7 +212,7 @@ enum turtle_return tamd_map_load_(struct turtle_map ** map, const char * path,
                                     "missing data when reading file `%s'" :
                                     ((strcmp(ext + 1, "hgt") == 0) ?
                                             "invalid hgt filename for `%s'" :
-                                            "not an uncompressed 16-bit strip TIFF: `%s'")));
+                                            "not a 16-bit strip TIFF this library reads: `%s'")));
                 if (rc == TURTLE_RETURN_BAD_FORMAT + 100) rc = TURTLE_RETURN_BAD_FORMAT;
                 return tamd_raise_(error, (enum turtle_return)rc, file, line, text, path);
         }

@@ -4,11 +4,14 @@
  * waits for the tiles it brings in [ref stack.c:399-450: the reference loads a
  * tile the moment a query needs it]; reading a 3601^2 tile, turning its byte
  * order and rows and laying its nodes out in blocks takes ~15 ms on one core.
- * So the tiles of a round are cut in BANDS of rows (formats whose rows sit at
- * known offsets: .hgt, uncompressed GeoTIFF) and a crew of worker threads takes
- * the bands, each read, decoded and laid out straight into a page-locked staging
- * buffer from which the upload is one copy.  Workers touch files and host memory
- * only: no device call.
+ * So the tiles of a round are cut in BANDS of rows (formats that can be read by
+ * rows: .hgt and GeoTIFF) and a crew of worker threads takes the bands, each
+ * read, decoded and laid out straight into a page-locked staging buffer from
+ * which the upload is one copy.  The rows of .hgt and uncompressed GeoTIFF sit at
+ * known offsets; a compressed GeoTIFF decodes by whole strips, so its bands are
+ * no lower than a strip (the probe's `rows_together`): no more bands than strips,
+ * and a strip is decoded by the two bands it may straddle at most.  Workers touch
+ * files and host memory only: no device call.
  */
 #define _GNU_SOURCE
 #include "host.h"
@@ -183,6 +186,8 @@ void tamd_tiles_decode(struct tamd_tile_job * jobs, int n)
                 /* whole block rows to a band */
                 int height = ((ny + count - 1) / count + TAMD_BLOCK - 1) / TAMD_BLOCK * TAMD_BLOCK;
                 if (height < TAMD_BLOCK) height = TAMD_BLOCK;
+                if (height < jobs[k].map->rows_together) /* (whole strips: see the header) */
+                        height = (jobs[k].map->rows_together + TAMD_BLOCK - 1) / TAMD_BLOCK * TAMD_BLOCK;
                 int iy;
                 for (iy = 0; iy < ny; iy += height) {
                         bands[n_bands].job = &jobs[k];
