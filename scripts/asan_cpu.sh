@@ -1,7 +1,7 @@
 #!/bin/bash
 # The host C objects under AddressSanitizer + UBSan, CPU tests only (no GPU needed; sanitizers are not
 # available on the GPU pool): builds /tmp/asan/libturtle_amd.so (host objects instrumented, the device
-# object as built) and runs the host-side tests against it; and the staging of the batch calls
+# objects as built) and runs the host-side tests against it; and the staging of the batch calls
 # (stage.c) against a stub of the device layer, instrumented as well.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -11,7 +11,7 @@ cd $ROOT/turtle_amd/csrc
 for f in *.c; do
   gcc -O1 -g -std=gnu99 -fPIC -fsanitize=address,undefined -fno-omit-frame-pointer -I../../include -I. -c $f -o /tmp/asan/${f%.c}.o
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o /tmp/asan/libturtle_amd.so /tmp/asan/*.o build/device.o -lm -lz -lpthread -fsanitize=address,undefined
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o /tmp/asan/libturtle_amd.so /tmp/asan/*.o build/device.o build/runtime.o -lm -lz -lpthread -fsanitize=address,undefined
 cd $ROOT
 # stage.c alone, against a host-memory stub of the device calls it uses (tests/c/stage_stub.c)
 python -m pytest tests/test_stage_host.py -x -q

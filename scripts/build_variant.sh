@@ -1,6 +1,7 @@
 #!/bin/bash
 # build_variant.sh <name> [-DFLAG ...]: a build of the library with extra flags, as variants/<name>.so
-# (no GPU needed; for A/B runs with TURTLE_AMD_LIBRARY)
+# (no GPU needed; for A/B runs with TURTLE_AMD_LIBRARY).  SRC= another device.hip; the thread runtime
+# (runtime.hip) and the host objects are the tree's own, as make built them
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift

@@ -14,7 +14,7 @@ CSRC = os.path.join(ROOT, "turtle_amd", "csrc")
 
 
 def _build(tmp, sanitizer):
-    """libturtle_amd with its host objects under `sanitizer` (the device object as built),
+    """libturtle_amd with its host objects under `sanitizer` (the device objects as built),
     and tests/c/host_stack_threads.c against it"""
     out = os.path.join(tmp, "san")
     os.makedirs(out, exist_ok=True)
@@ -27,7 +27,8 @@ def _build(tmp, sanitizer):
             subprocess.check_call(["gcc"] + flags + ["-c", os.path.join(CSRC, f), "-o", objs[-1]])
     lib = os.path.join(out, "libturtle_amd.so")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-o", lib] + objs +
-                          [os.path.join(CSRC, "build", "device.o"), "-lm", "-lz", "-lpthread",
+                          [os.path.join(CSRC, "build", "device.o"), os.path.join(CSRC, "build", "runtime.o"),
+                           "-lm", "-lz", "-lpthread",
                            f"-fsanitize={sanitizer}"])
     exe = os.path.join(out, "host_stack_threads")
     subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", f"-fsanitize={sanitizer}",

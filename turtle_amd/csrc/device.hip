@@ -1,7 +1,8 @@
 /*
- * device.hip -- the gfx950 device layer of libturtle_amd: HBM management, the
- * stream, and every kernel of the stepper path.  Written for CDNA4 (wave64);
- * no other target is supported.
+ * device.hip -- the gfx950 device layer of libturtle_amd: every kernel of the
+ * stepper path, and the layer that launches them.  (The calling thread's device,
+ * stream and memory: runtime.hip.)  Written for CDNA4 (wave64); no other target
+ * is supported.
  *
  * Arithmetic contract: the kernels evaluate the reference's expressions in
  * the reference's operand order in IEEE fp64 (this file is compiled with
@@ -34,15 +35,13 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/device/device_radix_sort.hpp>
 
-#include <sys/syscall.h>
-#include <unistd.h>
-
 #include <cfloat>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
+#include "device_ctx.h"
 #include "internal.h" /* includes turtle_amd_device.h: the device functions and the tables */
 
 using namespace turtle_amd_device;
@@ -2455,80 +2454,12 @@ __global__ void k_unblock(const uint16_t * __restrict__ blocked, int nx, int ny,
 } /* namespace */
 
 /* ======================================================================== */
-/*                         host side of the device layer                    */
+/*                             the launch layer                             */
 /* ======================================================================== */
 
-/* Per host THREAD: the device it works on, its stream, its scratch arena and
- * its blocks of bookkeeping memory.  The reference's rule is one stepper (and one
- * client) per thread over shared maps and stacks [ref include/turtle.h:129-132,
- * :620-626, examples/example-pthread.c:66-125]; here a thread also has a device:
- * the one LOCAL_RANK names (else 0) until it calls turtle_amd_device_set, so one
- * process can drive several GPUs, a thread each.  What threads share -- map
- * nodes, a stack's tiles -- is uploaded per device and changed under one lock
- * (host.h: tamd_geometry_lock). */
-struct Ctx {
-        int device = -1, cus = 0;
-        hipStream_t own_stream = nullptr, stream = nullptr;
-        int math_strict = 0;
-        int in_flight = 1; /* batches the thread keeps in flight (tamd_dev_in_flight_set) */
-        void * scratch = nullptr;
-        size_t scratch_size = 0, scratch_used = 0;
-        void * block[2] = { nullptr, nullptr }; /* grow-only: the pager's lists, a stack's own tables */
-        size_t block_size[2] = { 0, 0 };
-        void * pinned = nullptr; /* host memory the device can copy from / to without staging */
-        size_t pinned_size = 0;
-        void release()
-        {
-                if (device < 0) return;
-                if (hipSetDevice(device) != hipSuccess) return;
-                if (own_stream != nullptr) (void)hipStreamSynchronize(own_stream), (void)hipStreamDestroy(own_stream);
-                if (scratch != nullptr) (void)hipFree(scratch);
-                for (int i = 0; i < 2; i++)
-                        if (block[i] != nullptr) (void)hipFree(block[i]);
-                if (pinned != nullptr) (void)hipHostFree(pinned);
-                pinned = nullptr, pinned_size = 0;
-                own_stream = stream = nullptr, scratch = nullptr, scratch_size = scratch_used = 0;
-                block[0] = block[1] = nullptr, block_size[0] = block_size[1] = 0;
-        }
-};
-static thread_local char g_error[512] = "";
-static thread_local Ctx g_ctx;
-/* A thread that ends without turtle_amd_thread_release() (a pool's worker, an OpenMP
- * thread) gives back its stream, arena, blocks and pinned buffer here -- while the
- * process lives: at process exit the HIP runtime may already be gone, and the
- * main thread's context is left to it. */
-static thread_local struct CtxGuard {
-        bool armed = false; /* (set by tamd_dev_select on any thread but the main one) */
-        ~CtxGuard()
-        {
-                if (armed) g_ctx.release();
-        }
-} g_ctx_guard;
 #define g_stream (g_ctx.stream)
 #define g_cus (g_ctx.cus)
 #define g_math_strict (g_ctx.math_strict)
-
-static int fail(const char * what, hipError_t e)
-{
-        snprintf(g_error, sizeof(g_error), "%s: %s (HIP error %d)", what,
-            hipGetErrorString(e), (int)e);
-        return 1;
-}
-
-#define HIP_TRY(call)                                                          \
-        do {                                                                   \
-                const hipError_t e_ = (call);                                  \
-                if (e_ != hipSuccess) return fail(#call, e_);                  \
-        } while (0)
-
-extern "C" const char * tamd_dev_error(void) { return g_error; }
-
-extern "C" int tamd_dev_count(void)
-{
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess) return 0;
-        return count;
-}
 
 #ifdef TRACE_POOL_STATS
 extern "C" int tamd_dev_pool_stats(unsigned long long * out, int reset)
@@ -2542,235 +2473,6 @@ extern "C" int tamd_dev_pool_stats(unsigned long long * out, int reset)
 }
 #endif
 
-extern "C" int tamd_dev_select(int device)
-{
-        const int count = tamd_dev_count();
-        if (count <= 0) {
-                snprintf(g_error, sizeof(g_error),
-                    "no HIP device is visible: libturtle_amd has no CPU path");
-                return 1;
-        }
-        if ((device < 0) || (device >= count)) {
-                snprintf(g_error, sizeof(g_error),
-                    "invalid device index %d (have %d)", device, count);
-                return 1;
-        }
-        if (g_ctx.device == device) {
-                HIP_TRY(hipSetDevice(device));
-                return 0;
-        }
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, device));
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-                snprintf(g_error, sizeof(g_error),
-                    "device %d is %s: libturtle_amd carries gfx950 code only",
-                    device, prop.gcnArchName);
-                return 1;
-        }
-        /* what this thread held on its previous device goes (its stream too: a
-         * stream handed in by turtle_amd_stream_set belonged to that device) */
-        g_ctx.release();
-        HIP_TRY(hipSetDevice(device));
-        g_ctx.device = device;
-        g_ctx_guard.armed = ((long)syscall(SYS_gettid) != (long)getpid()); /* not the main thread: see CtxGuard */
-        g_ctx.cus = prop.multiProcessorCount;
-        HIP_TRY(hipStreamCreateWithFlags(&g_ctx.own_stream, hipStreamNonBlocking));
-        g_ctx.stream = g_ctx.own_stream;
-        return 0;
-}
-
-extern "C" int tamd_dev_init(void)
-{
-        if (g_ctx.device >= 0) {
-                HIP_TRY(hipSetDevice(g_ctx.device)); /* HIP's current device is per thread too */
-                return 0;
-        }
-        int device = 0;
-        const char * env = getenv("LOCAL_RANK");
-        if ((env != nullptr) && (*env != 0)) {
-                const int count = tamd_dev_count();
-                if (count > 0) device = atoi(env) % count;
-        }
-        return tamd_dev_select(device);
-}
-
-extern "C" int tamd_dev_current(void) { return g_ctx.device; }
-
-/* what the calling thread holds on its device (a worker calls it before it ends:
- * nothing is freed behind a thread's back, the runtime may be gone by then) */
-extern "C" void tamd_dev_release(void)
-{
-        g_ctx.release();
-        g_ctx.device = -1;
-}
-extern "C" int tamd_dev_cus(void) { return (tamd_dev_init() == 0) ? g_ctx.cus : 0; }
-
-extern "C" int tamd_dev_stream_set(void * stream)
-{
-        if (tamd_dev_init()) return 1;
-        g_ctx.stream = (stream != nullptr) ? (hipStream_t)stream : g_ctx.own_stream;
-        return 0;
-}
-
-extern "C" int tamd_dev_sync(void)
-{
-        if (tamd_dev_init()) return 1;
-        HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-        return 0;
-}
-
-/* every stream of `device` (before memory that other threads' launches may still
- * read is freed); leaves the calling thread on its own device */
-/* Every stream of that device has drained (non-zero: it could not be told -- the
- * caller then LEAKS what it meant to free there, rather than free memory that a
- * launch may still read).  The calling thread is back on its own device on every
- * path. */
-extern "C" int tamd_dev_sync_device(int device)
-{
-        if (device < 0) return 0;
-        hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if ((g_ctx.device >= 0) && (g_ctx.device != device)) {
-                const hipError_t back = hipSetDevice(g_ctx.device);
-                if (e == hipSuccess) e = back;
-        }
-        return (e == hipSuccess) ? 0 : fail("tamd_dev_sync_device", e);
-}
-
-extern "C" int tamd_dev_malloc(void ** ptr, size_t bytes)
-{
-        *ptr = nullptr;
-        if (tamd_dev_init()) return 1;
-        HIP_TRY(hipMalloc(ptr, bytes ? bytes : 1));
-        return 0;
-}
-
-extern "C" void tamd_dev_free(void * ptr)
-{
-        if (ptr != nullptr) (void)hipFree(ptr);
-}
-
-/* memory of another device than the calling thread's */
-extern "C" void tamd_dev_free_on(int device, void * ptr)
-{
-        if (ptr == nullptr) return;
-        if ((device >= 0) && (device != g_ctx.device)) (void)hipSetDevice(device);
-        (void)hipFree(ptr);
-        if ((device >= 0) && (device != g_ctx.device) && (g_ctx.device >= 0)) (void)hipSetDevice(g_ctx.device);
-}
-
-extern "C" int tamd_dev_h2d(void * dst, const void * src, size_t bytes)
-{
-        if (tamd_dev_init()) return 1;
-        if (bytes == 0) return 0;
-        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, g_ctx.stream));
-        HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-        return 0;
-}
-
-extern "C" int tamd_dev_d2h(void * dst, const void * src, size_t bytes)
-{
-        if (tamd_dev_init()) return 1;
-        if (bytes == 0) return 0;
-        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, g_ctx.stream));
-        HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-        return 0;
-}
-
-extern "C" int tamd_dev_zero(void * dst, size_t bytes)
-{
-        if (tamd_dev_init()) return 1;
-        HIP_TRY(hipMemsetAsync(dst, 0, bytes, g_ctx.stream));
-        return 0;
-}
-
-extern "C" int tamd_dev_pinned(void ** ptr, size_t bytes)
-{
-        *ptr = nullptr;
-        if (tamd_dev_init()) return 1;
-        if (bytes > g_ctx.pinned_size) {
-                HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-                if (g_ctx.pinned != nullptr) (void)hipHostFree(g_ctx.pinned);
-                g_ctx.pinned = nullptr, g_ctx.pinned_size = 0;
-                HIP_TRY(hipHostMalloc(&g_ctx.pinned, bytes, hipHostMallocDefault));
-                g_ctx.pinned_size = bytes;
-        }
-        *ptr = g_ctx.pinned;
-        return 0;
-}
-
-/* page-locked host memory that outlives the call (a stack's staging buffers for its
- * tiles: a copy from it is queued, not waited for) */
-extern "C" int tamd_dev_host_alloc(void ** ptr, size_t bytes)
-{
-        *ptr = nullptr;
-        if (tamd_dev_init()) return 1;
-        HIP_TRY(hipHostMalloc(ptr, bytes, hipHostMallocDefault));
-        return 0;
-}
-
-extern "C" void tamd_dev_host_free(void * ptr)
-{
-        if (ptr != nullptr) (void)hipHostFree(ptr);
-}
-
-extern "C" int tamd_dev_copy_async(void * dst, const void * src, size_t bytes, int to_device)
-{
-        if (tamd_dev_init()) return 1;
-        if (bytes == 0) return 0;
-        HIP_TRY(hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost,
-            g_ctx.stream));
-        return 0;
-}
-
-extern "C" void tamd_scratch_reset(void) { g_ctx.scratch_used = 0; }
-
-extern "C" int tamd_scratch_get(void ** ptr, size_t bytes)
-{
-        *ptr = nullptr;
-        if (tamd_dev_init()) return 1;
-        const size_t need = (bytes + 255) & ~(size_t)255;
-        if (g_ctx.scratch_used + need > g_ctx.scratch_size) {
-                if (g_ctx.scratch_used != 0) {
-                        /* pieces already handed out would dangle: the host layer
-                         * sizes the arena up front with one oversize request */
-                        snprintf(g_error, sizeof(g_error), "scratch arena exhausted");
-                        return 1;
-                }
-                HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-                if (g_ctx.scratch) (void)hipFree(g_ctx.scratch);
-                g_ctx.scratch = nullptr, g_ctx.scratch_size = 0;
-                const size_t size = need + (need >> 2) + (1u << 20);
-                HIP_TRY(hipMalloc(&g_ctx.scratch, size));
-                g_ctx.scratch_size = size;
-        }
-        *ptr = (char *)g_ctx.scratch + g_ctx.scratch_used;
-        g_ctx.scratch_used += need;
-        return 0;
-}
-
-/* One of the calling thread's grow-only blocks (0: the pager's lists and counters,
- * 1: the tables of a stack's own batch calls), at least `bytes` long; *grown is
- * set when it is a new allocation (what it held is gone) */
-extern "C" int tamd_dev_block(int which, void ** ptr, size_t bytes, int * grown)
-{
-        *ptr = nullptr;
-        if (grown != nullptr) *grown = 0;
-        if (tamd_dev_init()) return 1;
-        if (bytes > g_ctx.block_size[which]) {
-                if (g_ctx.block[which] != nullptr) {
-                        HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-                        (void)hipFree(g_ctx.block[which]);
-                        g_ctx.block[which] = nullptr, g_ctx.block_size[which] = 0;
-                }
-                HIP_TRY(hipMalloc(&g_ctx.block[which], bytes));
-                g_ctx.block_size[which] = bytes;
-                if (grown != nullptr) *grown = 1;
-        }
-        *ptr = g_ctx.block[which];
-        return 0;
-}
-
 static int grid_for(long n, int block)
 {
         long blocks = (n + block - 1) / block;
@@ -2781,11 +2483,23 @@ static int grid_for(long n, int block)
         return (int)blocks;
 }
 
-#define LAUNCH_CHECK(name)                                                     \
-        do {                                                                   \
-                const hipError_t e_ = hipGetLastError();                       \
-                if (e_ != hipSuccess) return fail("launch " name, e_);         \
-        } while (0)
+/* `blocks` blocks of 256 threads of a kernel, on the calling thread's stream */
+template <class... P, class... A>
+static int launch_blocks(const char * name, void (*kernel)(P...), unsigned blocks, size_t lds_bytes,
+    const A &... args)
+{
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds_bytes, g_stream, args...);
+        LAUNCH_CHECK(name);
+        return 0;
+}
+/* A whole flat entry point: n items, each the work of one thread (none: nothing to do) */
+template <class... P, class... A>
+static int launch_items(const char * name, void (*kernel)(P...), long n, size_t lds_bytes, const A &... args)
+{
+        if (tamd_dev_init()) return 1;
+        if (n <= 0) return 0;
+        return launch_blocks(name, kernel, grid_for(n, 256), lds_bytes, args...);
+}
 
 /* A run-time value that a kernel takes as a template parameter: f is called with the
  * std::integral_constant of the first of VALUES that equals `value`, or of the last. */
@@ -2803,97 +2517,66 @@ static int with_mode(int mode, F && f)
         return with_constant<TAMD_MODE_ONE_MAP, TAMD_MODE_ONE_STACK, TAMD_MODE_GENERIC>(mode, f);
 }
 
+/* ... the arithmetic (Strict, else Fast: a kernel's FAST) */
+typedef std::integral_constant<int, 0> Strict;
+typedef std::integral_constant<int, 1> Fast;
+template <class F>
+static int with_math(bool strict, F && f)
+{
+        return with_constant<Strict::value, Fast::value>(strict ? Strict::value : Fast::value, f);
+}
+
 extern "C" int tamd_k_ecef_from_geodetic(long n, const double * lat,
     const double * lon, const double * elev, double * ecef)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_ecef_from_geodetic, dim3(grid_for(n, 256)), dim3(256), 0,
-            g_stream, n, lat, lon, elev, ecef);
-        LAUNCH_CHECK("k_ecef_from_geodetic");
-        return 0;
+        return launch_items("k_ecef_from_geodetic", k_ecef_from_geodetic, n, 0, n, lat, lon, elev, ecef);
 }
 
 extern "C" int tamd_k_ecef_to_geodetic(
     long n, const double * ecef, double * lat, double * lon, double * alt)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        if (g_math_strict)
-                hipLaunchKernelGGL(k_ecef_to_geodetic<false>, dim3(grid_for(n, 256)),
-                    dim3(256), 0, g_stream, n, ecef, lat, lon, alt);
-        else
-                hipLaunchKernelGGL(k_ecef_to_geodetic<true>, dim3(grid_for(n, 256)),
-                    dim3(256), 0, g_stream, n, ecef, lat, lon, alt);
-        LAUNCH_CHECK("k_ecef_to_geodetic");
-        return 0;
+        return with_math(g_math_strict, [&](auto fast) {
+                return launch_items("k_ecef_to_geodetic", k_ecef_to_geodetic<decltype(fast)::value>, n, 0, n,
+                    ecef, lat, lon, alt);
+        });
 }
 
 extern "C" int tamd_k_ecef_from_horizontal(long n, const double * lat,
     const double * lon, const double * az, const double * el, double * dir)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_ecef_from_horizontal, dim3(grid_for(n, 256)), dim3(256), 0,
-            g_stream, n, lat, lon, az, el, dir);
-        LAUNCH_CHECK("k_ecef_from_horizontal");
-        return 0;
+        return launch_items("k_ecef_from_horizontal", k_ecef_from_horizontal, n, 0, n, lat, lon, az, el, dir);
 }
 
 extern "C" int tamd_k_ecef_to_horizontal(long n, const double * lat,
     const double * lon, const double * dir, double * az, double * el)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_ecef_to_horizontal, dim3(grid_for(n, 256)), dim3(256), 0,
-            g_stream, n, lat, lon, dir, az, el);
-        LAUNCH_CHECK("k_ecef_to_horizontal");
-        return 0;
+        return launch_items("k_ecef_to_horizontal", k_ecef_to_horizontal, n, 0, n, lat, lon, dir, az, el);
 }
 
 extern "C" int tamd_k_elevation(struct tamd_view view, long n, const double * a,
     const double * b, double * z, int * inside, struct tamd_paging pg)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_elevation, dim3(grid_for(n, 256)), dim3(256), 0, g_stream,
-            view, n, a, b, z, inside, pg);
-        LAUNCH_CHECK("k_elevation");
-        return 0;
+        return launch_items("k_elevation", k_elevation, n, 0, view, n, a, b, z, inside, pg);
 }
 
 extern "C" int tamd_k_project(struct tamd_proj proj, int inverse, long n, const double * a,
     const double * b, double * c, double * d)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_project, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, proj,
-            inverse, n, a, b, c, d);
-        LAUNCH_CHECK("k_project");
-        return 0;
+        return launch_items("k_project", k_project, n, 0, proj, inverse, n, a, b, c, d);
 }
 
 extern "C" int tamd_k_gradient(struct tamd_view view, long n, const double * a,
     const double * b, double * ga, double * gb, int * inside, struct tamd_paging pg)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_gradient, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, view,
-            n, a, b, ga, gb, inside, pg);
-        LAUNCH_CHECK("k_gradient");
-        return 0;
+        return launch_items("k_gradient", k_gradient, n, 0, view, n, a, b, ga, gb, inside, pg);
 }
 
 extern "C" int tamd_k_position(struct tamd_view view, long n, const double * lat,
     const double * lon, const double * height, int layer, double * pos,
     int * data_index, struct tamd_paging pg)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_position, dim3(grid_for(n, 256)), dim3(256), 0, g_stream,
-            view, n, lat, lon, height, layer, pos, data_index, pg);
-        LAUNCH_CHECK("k_position");
-        return 0;
+        return launch_items("k_position", k_position, n, 0, view, n, lat, lon, height, layer, pos,
+            data_index, pg);
 }
 
 /* n single steps: the step kernel, then -- with a direction and scratch for
@@ -2903,32 +2586,24 @@ static int run_step(struct tamd_view view, long n, double * pos, const double * 
     double * lat, double * lon, double * alt, double * elev, double * step, int * index,
     int flags, CrossList cross, Paging pg, ull * stats, StepWalk walk)
 {
-        const dim3 grid(grid_for(n, 256)), block(256);
         const bool strict = g_math_strict || !view.fast_ok;
         return with_mode(view.mode, [&](auto mode) {
                 constexpr int MODE = decltype(mode)::value;
-                if (strict)
-                        hipLaunchKernelGGL((k_step<MODE, false>), grid, block, 0, g_stream, view, n,
-                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk);
-                else if (MODE == TAMD_MODE_GENERIC)
-                        hipLaunchKernelGGL((k_step<MODE, true>), grid, block, 0, g_stream, view, n,
-                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk);
-                else
-                        hipLaunchKernelGGL((k_step_fast<MODE>), grid, block, 0, g_stream, view, n,
-                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk);
-                LAUNCH_CHECK("k_step");
+                /* (the fast step of one map / one stack is a kernel of its own: see k_step_fast) */
+                const auto kernel = strict          ? k_step<MODE, false> :
+                    (MODE == TAMD_MODE_GENERIC) ? k_step<MODE, true> :
+                                                  k_step_fast<MODE>;
+                if (launch_blocks("k_step", kernel, grid_for(n, 256), 0, view, n, pos, dir, lat, lon, alt, elev,
+                        step, index, flags, cross, pg, stats, walk))
+                        return 1;
                 if (cross.ray == nullptr) return 0;
                 /* the listed rays are a few percent of n, and their number is on the
                  * device: a grid for a tenth of n, striding over whatever there is */
-                const dim3 few(grid_for(n / 10 + 1, 256));
-                if (strict)
-                        hipLaunchKernelGGL((k_bisect<MODE, false>), few, block, 0, g_stream, view,
-                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk);
-                else
-                        hipLaunchKernelGGL((k_bisect<MODE, true>), few, block, 0, g_stream, view,
-                            pos, dir, lat, lon, alt, elev, step, index, flags, cross, pg, stats, walk);
-                LAUNCH_CHECK("k_bisect");
-                return 0;
+                return with_math(strict, [&](auto fast) {
+                        return launch_blocks("k_bisect", k_bisect<MODE, decltype(fast)::value>,
+                            grid_for(n / 10 + 1, 256), 0, view, pos, dir, lat, lon, alt, elev, step, index, flags,
+                            cross, pg, stats, walk);
+                });
         });
 }
 
@@ -2963,34 +2638,30 @@ static int trace_blocks_per_cu(const void * kernel)
         return blocks;
 }
 
-extern "C" void tamd_dev_math_set(int strict) { g_ctx.math_strict = strict ? 1 : 0; }
-extern "C" void tamd_dev_in_flight_set(int batches) { g_ctx.in_flight = (batches > 1) ? batches : 1; }
-extern "C" int tamd_dev_in_flight_get(void) { return g_ctx.in_flight; }
-extern "C" int tamd_dev_math_get(void) { return g_ctx.math_strict; }
+/* The grid of a persistent kernel over n rays: the blocks that fit the chip, or that the
+ * rays can fill */
+template <class... P>
+static unsigned persistent_blocks(void (*kernel)(P...), long n)
+{
+        long blocks = (long)g_cus * trace_blocks_per_cu((const void *)kernel);
+        const long useful = (n + 255) / 256;
+        if (blocks > useful) blocks = useful;
+        return (unsigned)blocks;
+}
 
 template <int MODE, bool FAST, bool MODEL, bool PAGED, bool CROSS, bool POOL = false>
 static int launch_trace_(struct tamd_view view, long n, bool n_on_device, double * pos,
     const double * dir, int max_steps, int * index, double * length, int * n_steps,
     int flags, PhaseIO ph, ull * stats, ull * queue)
 {
-        const void * kernel = (const void *)k_trace<MODE, FAST, MODEL, PAGED, CROSS, POOL>;
-        long blocks = (long)g_cus * trace_blocks_per_cu(kernel);
-        const long useful = (n + 255) / 256;
-        if (!n_on_device && (blocks > useful)) blocks = useful;
-        if (n_on_device) {
-                /* phase B: the rays phase A handed over -- the long ones (a few
-                 * percent of n) and whatever was in flight when its queue ran dry
-                 * (up to one ray per lane): as many blocks as fit, or as there can
-                 * be work for */
-                long wide = useful;
-                if (wide < (long)g_cus) wide = (long)g_cus;
-                if (blocks > wide) blocks = wide;
-        }
-        hipLaunchKernelGGL((k_trace<MODE, FAST, MODEL, PAGED, CROSS, POOL>), dim3((unsigned)blocks), dim3(256),
-            0, g_stream, view, n, pos, dir, max_steps, index, length, n_steps, flags, ph, stats,
-            queue);
-        LAUNCH_CHECK("k_trace");
-        return 0;
+        /* phase B (n on the device): the rays phase A handed over -- the long ones (a few
+         * percent of n) and whatever was in flight when its queue ran dry
+         * (up to one ray per lane): as many blocks as fit, or as there can
+         * be work for, which is a block a CU at the least */
+        const long fill = (n_on_device && (n < 256L * g_cus)) ? 256L * g_cus : n;
+        const auto kernel = k_trace<MODE, FAST, MODEL, PAGED, CROSS, POOL>;
+        return launch_blocks("k_trace", kernel, persistent_blocks(kernel, fill), 0, view, n, pos, dir, max_steps,
+            index, length, n_steps, flags, ph, stats, queue);
 }
 
 /* the instance for this call: PAGED where tiles may have to come in, CROSS where
@@ -3031,20 +2702,14 @@ static int launch_cross(struct tamd_view view, long n, double * pos, const doubl
 {
         constexpr bool CAN_PAGE = (MODE != TAMD_MODE_ONE_MAP);
         const bool paged = CAN_PAGE && (pg.faulted != nullptr);
-        const void * kernel = paged ? (const void *)k_cross<MODE, FAST, CAN_PAGE> :
-                                      (const void *)k_cross<MODE, FAST, false>;
-        long blocks = (long)g_cus * trace_blocks_per_cu(kernel);
-        const long useful = (n + 255) / 256;
-        if (blocks > useful) blocks = useful;
-        if (paged)
-                hipLaunchKernelGGL((k_cross<MODE, FAST, CAN_PAGE>), dim3((unsigned)blocks), dim3(256), 0,
-                    g_stream, view, pos, dir, index, length, n_steps, cross, pg, stats, out);
-        else
-                hipLaunchKernelGGL((k_cross<MODE, FAST, false>), dim3((unsigned)blocks), dim3(256), 0,
-                    g_stream, view, pos, dir, index, length, n_steps, cross, pg, stats, out);
-        LAUNCH_CHECK("k_cross");
-        return 0;
+        const auto kernel = paged ? k_cross<MODE, FAST, CAN_PAGE> : k_cross<MODE, FAST, false>;
+        return launch_blocks("k_cross", kernel, persistent_blocks(kernel, n), 0, view, pos, dir, index, length,
+            n_steps, cross, pg, stats, out);
 }
+
+/* ---- the launch policy ---------------------------------------------------
+ *
+ * What a trace's launches are sized and ordered by: each figure with what was measured for it. */
 
 /* A run-time knob: an environment variable holding a number, read once per process;
  * `fallback` where it is unset or empty. */
@@ -3187,24 +2852,20 @@ static int run_trace(struct tamd_view view, long n, double * pos, const double *
         const CrossList cross = { parked + n, cross_ds, queue + 3 * kQ, parked + 2 * n };
         const PhaseIO one = { pg.ids, pg.n_in, nullptr, nullptr, 0, resume, pg, 0, 0, kChunk,
                 creep_lanes(n), dense_go(), listed ? cross : none };
-        if (!listed) {
-                if (strict)
-                        return launch_trace<MODE, false, false>(view, n, again, pos, dir, max_steps, index,
-                            length, n_steps, flags, one, stats, queue);
-                return launch_trace<MODE, true, false>(view, n, again, pos, dir, max_steps, index,
-                    length, n_steps, flags, one, stats, queue);
-        }
+        /* the pass that takes the rays as the call has them (in the arrays of the moment: the
+         * spatial order below puts its own in their place) */
+        const auto first_pass = [&](auto fast, const PhaseIO & ph) {
+                return launch_trace<MODE, decltype(fast)::value, false>(view, n, again, pos, dir, max_steps, index,
+                    length, n_steps, flags, ph, stats, queue);
+        };
+        if (!listed) return with_math(strict, [&](auto fast) { return first_pass(fast, one); });
         if (strict) {
-                if (launch_trace<MODE, false, false>(view, n, again, pos, dir, max_steps, index, length,
-                        n_steps, flags, one, stats, queue))
-                        return 1;
+                if (first_pass(Strict(), one)) return 1;
                 return launch_cross<MODE, false>(view, n, pos, dir, index, length, n_steps, cross, pg, stats);
         }
         const int park = park_threshold(MODE);
         if ((park <= 0) || (max_steps <= park)) {
-                if (launch_trace<MODE, true, false>(view, n, again, pos, dir, max_steps, index, length,
-                        n_steps, flags, one, stats, queue))
-                        return 1;
+                if (first_pass(Fast(), one)) return 1;
                 return launch_cross<MODE, true>(view, n, pos, dir, index, length, n_steps, cross, pg, stats);
         }
         PhaseIO a = { pg.ids, pg.n_in, parked, queue + 2 * kQ, park, resume, pg, kDrainLanes, 0,
@@ -3286,9 +2947,7 @@ static int run_trace(struct tamd_view view, long n, double * pos, const double *
                         HIP_TRY(hipMemsetAsync(keys.Current(), 0xFE, (size_t)n, g_stream));
                 }
         }
-        if (launch_trace<MODE, true, false>(view, n, again, pos, dir, max_steps, index, length,
-                n_steps, flags, a, stats, queue))
-                return 1;
+        if (first_pass(Fast(), a)) return 1;
         if (sorting) {
                 if (hipcub::DeviceRadixSort::SortPairs(sort_temp, temp_bytes, keys, ids, (int)n, 0, 8, g_stream) !=
                     hipSuccess)
@@ -3379,38 +3038,23 @@ extern "C" int tamd_k_walk(struct tamd_view view, long n, double * pos, double *
         const WalkIO io = { seed, first, first_step, n_steps };
         const bool strict = g_math_strict || !view.fast_ok;
         return with_mode(view.mode, [&](auto mode) {
-                constexpr int MODE = decltype(mode)::value;
-                const void * kernel = strict ? (const void *)k_walk<MODE, false> :
-                                               (const void *)k_walk<MODE, true>;
-                long blocks = (long)g_cus * trace_blocks_per_cu(kernel);
-                const long useful = (n + 255) / 256;
-                if (blocks > useful) blocks = useful;
-                if (strict)
-                        hipLaunchKernelGGL((k_walk<MODE, false>), dim3((unsigned)blocks), dim3(256), 0,
-                            g_stream, view, n, pos, alt, elev, index, length, steps, io, stats, queue);
-                else
-                        hipLaunchKernelGGL((k_walk<MODE, true>), dim3((unsigned)blocks), dim3(256), 0,
-                            g_stream, view, n, pos, alt, elev, index, length, steps, io, stats, queue);
-                LAUNCH_CHECK("k_walk");
-                return 0;
+                return with_math(strict, [&](auto fast) {
+                        const auto kernel = k_walk<decltype(mode)::value, decltype(fast)::value>;
+                        return launch_blocks("k_walk", kernel, persistent_blocks(kernel, n), 0, view, n, pos, alt,
+                            elev, index, length, steps, io, stats, queue);
+                });
         });
 }
 
 template <int MODE, bool REC>
-static void launch_traverse(const tamd_view & view, long n, double * pos, int * index, const TraverseIO & io,
+static int launch_traverse(const tamd_view & view, long n, double * pos, int * index, const TraverseIO & io,
     ull * stats, ull * queue, bool strict, typename CrossingsArg<REC>::type rec)
 {
-        const void * kernel = strict ? (const void *)k_traverse<MODE, false, REC> :
-                                       (const void *)k_traverse<MODE, true, REC>;
-        long blocks = (long)g_cus * trace_blocks_per_cu(kernel);
-        const long useful = (n + 255) / 256;
-        if (blocks > useful) blocks = useful;
-        if (strict)
-                hipLaunchKernelGGL((k_traverse<MODE, false, REC>), dim3((unsigned)blocks), dim3(256), 0,
-                    g_stream, view, n, pos, index, io, stats, queue, rec);
-        else
-                hipLaunchKernelGGL((k_traverse<MODE, true, REC>), dim3((unsigned)blocks), dim3(256), 0,
-                    g_stream, view, n, pos, index, io, stats, queue, rec);
+        return with_math(strict, [&](auto fast) {
+                const auto kernel = k_traverse<MODE, decltype(fast)::value, REC>;
+                return launch_blocks("k_traverse", kernel, persistent_blocks(kernel, n), 0, view, n, pos, index, io,
+                    stats, queue, rec);
+        });
 }
 
 /* A whole traverse in one launch (k_traverse): every tile resident, nothing listed */
@@ -3427,12 +3071,8 @@ extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, cons
         return with_mode(view.mode, [&](auto mode) {
                 constexpr int MODE = decltype(mode)::value;
                 if (rec != nullptr)
-                        launch_traverse<MODE, true>(view, n, pos, index, io, stats, queue, strict, *rec);
-                else
-                        launch_traverse<MODE, false>(view, n, pos, index, io, stats, queue, strict,
-                            NoCrossings());
-                LAUNCH_CHECK("k_traverse");
-                return 0;
+                        return launch_traverse<MODE, true>(view, n, pos, index, io, stats, queue, strict, *rec);
+                return launch_traverse<MODE, false>(view, n, pos, index, io, stats, queue, strict, NoCrossings());
         });
 }
 
@@ -3455,46 +3095,27 @@ extern "C" int tamd_k_traverse_gen(long n, int first, const double * alt, const 
     int * live_index, int * medium, int * index, double * length, int * n_steps, int * n_cross,
     double ceiling, int max_steps, unsigned long long * counters)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_traverse_gen, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, n, first,
-            alt, step, live_index, medium, index, length, n_steps, n_cross, ceiling, max_steps,
-            counters);
-        LAUNCH_CHECK("k_traverse_gen");
-        return 0;
+        return launch_items("k_traverse_gen", k_traverse_gen, n, 0, n, first, alt, step, live_index, medium,
+            index, length, n_steps, n_cross, ceiling, max_steps, counters);
 }
 
 extern "C" int tamd_k_crossings_gen(long n, const double * pos, const double * step, const int * live_index,
     const int * medium, const int * n_cross, double * total, struct tamd_crossings rec)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_crossings_gen, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, n, pos, step,
-            live_index, medium, n_cross, total, rec);
-        LAUNCH_CHECK("k_crossings_gen");
-        return 0;
+        return launch_items("k_crossings_gen", k_crossings_gen, n, 0, n, pos, step, live_index, medium, n_cross,
+            total, rec);
 }
 
 extern "C" int tamd_k_philox(long n, unsigned long long seed, unsigned long long stream,
     long first, unsigned * out)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_philox, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, n, seed,
-            stream, first, out);
-        LAUNCH_CHECK("k_philox");
-        return 0;
+        return launch_items("k_philox", k_philox, n, 0, n, seed, stream, first, out);
 }
 
 extern "C" int tamd_k_isotropic(long n, unsigned long long seed, unsigned long long stream,
     long first, double * dir)
 {
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_isotropic, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, n,
-            seed, stream, first, dir);
-        LAUNCH_CHECK("k_isotropic");
-        return 0;
+        return launch_items("k_isotropic", k_isotropic, n, 0, n, seed, stream, first, dir);
 }
 
 extern "C" int tamd_k_tally(long n, const int * index, const double * length,
@@ -3509,10 +3130,8 @@ extern "C" int tamd_k_tally(long n, const int * index, const double * length,
                 return 1;
         }
         const double scale = (double)n_bins / length_max;
-        hipLaunchKernelGGL(k_tally, dim3(grid_for(n, 256)), dim3(256), lds, g_stream, n,
-            index, length, n_media, hits, n_bins, scale, histogram);
-        LAUNCH_CHECK("k_tally");
-        return 0;
+        return launch_blocks("k_tally", k_tally, grid_for(n, 256), lds, n, index, length, n_media, hits, n_bins, scale,
+            histogram);
 }
 
 extern "C" int tamd_k_resample(struct tamd_view view, const struct tamd_grid * grids, int from_map,
@@ -3524,25 +3143,16 @@ extern "C" int tamd_k_resample(struct tamd_view view, const struct tamd_grid * g
         /* the target's projection: a host field, read back from its table */
         struct tamd_grid target;
         if (tamd_dev_d2h(&target, grids, sizeof(target))) return 1;
-        const dim3 blocks(grid_for(n_blocks * 64, 256));
+        const unsigned blocks = grid_for(n_blocks * 64, 256);
         return with_constant<RS_MAP, RS_STACK>(from_map ? RS_MAP : RS_STACK, [&](auto source) {
                 return with_constant<TAMD_PROJ_LAMBERT, TAMD_PROJ_UTM, TAMD_PROJ_NONE>(target.proj.type, [&](auto type) {
-                        hipLaunchKernelGGL((k_resample<decltype(source)::value, decltype(type)::value>), blocks,
-                            dim3(256), 0, g_stream, view, grids, z0, dz, is_signed, flags, n_blocks, out, pg,
-                            counters);
-                        LAUNCH_CHECK("k_resample");
-                        return 0;
+                        return launch_blocks("k_resample", k_resample<decltype(source)::value, decltype(type)::value>,
+                            blocks, 0, view, grids, z0, dz, is_signed, flags, n_blocks, out, pg, counters);
                 });
         });
 }
 
 extern "C" int tamd_k_unblock(const uint16_t * blocked, int nx, int ny, int nbx, uint16_t * rows)
 {
-        if (tamd_dev_init()) return 1;
-        const long n = (long)nx * ny;
-        if (n <= 0) return 0;
-        hipLaunchKernelGGL(k_unblock, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, blocked, nx, ny,
-            nbx, rows);
-        LAUNCH_CHECK("k_unblock");
-        return 0;
+        return launch_items("k_unblock", k_unblock, (long)nx * ny, 0, blocked, nx, ny, nbx, rows);
 }

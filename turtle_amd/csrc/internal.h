@@ -6,8 +6,8 @@
  *   host (C99: error.c map.c hgt.c stack.c client.c stepper.c ecef.c batch.c)
  *        owns the opaque handles of the public API, file ingest, the error
  *        convention, and flattening a stepper into the POD tables below;
- *   device (device.hip) owns HBM, the stream, and every kernel.  All
- *        arithmetic of the path happens there.
+ *   device (runtime.hip: HBM and the stream; device.hip: every kernel and its
+ *        launch).  All arithmetic of the path happens there.
  */
 #ifndef TURTLE_AMD_INTERNAL_H
 #define TURTLE_AMD_INTERNAL_H
@@ -24,12 +24,12 @@ extern "C" {
 
 
 /* ------------------------------------------------------------------------ */
-/* Device layer (device.hip).  Every function returns 0 on success or a     */
+/* Device layer (runtime.hip, device.hip).  Each returns 0 on success or a   */
 /* non-zero value after recording a message readable with tamd_dev_error(). */
 /* ------------------------------------------------------------------------ */
 
 /* The device, the stream, the arithmetic mode, the scratch arena and the blocks
- * below belong to the calling THREAD (device.hip: struct Ctx). */
+ * below belong to the calling THREAD (runtime.hip; device_ctx.h: struct Ctx). */
 const char * tamd_dev_error(void);
 int tamd_dev_init(void);   /* idempotent; selects the thread's device, makes its stream */
 void tamd_dev_release(void); /* frees what the calling thread holds on its device */
@@ -46,7 +46,7 @@ int tamd_dev_stream_set(void * stream);
 int tamd_dev_sync(void);
 void tamd_dev_math_set(int strict); /* 1: reference-order arithmetic in k_trace */
 int tamd_dev_math_get(void);
-void tamd_dev_in_flight_set(int batches); /* the batches the thread keeps in flight (a hint: device.hip) */
+void tamd_dev_in_flight_set(int batches); /* the batches the thread keeps in flight (a hint: device.hip, trace_blocks_per_cu) */
 int tamd_dev_in_flight_get(void);
 
 int tamd_dev_malloc(void ** ptr, size_t bytes);
