@@ -10,7 +10,9 @@
  * given on the command line (an .hgt file; default N45E003.hgt); the fan is 36
  * azimuths x 6 elevations from 0 to 25 degrees, up to a 2000 m ceiling.  For
  * each ray that meets rock it prints the first entry into the rock (medium 0)
- * and the last exit from it (into the air or out of the data).
+ * and the last exit from it (into the air or out of the data), and -- from one
+ * turtle_stepper_normal_n call on the first crossing of every ray -- the cosine
+ * of the angle between the ray and the normal of the surface it crossed there.
  *
  *   cc -Iinclude examples/exit_points.c -Lturtle_amd -lturtle_amd -lm \
  *      -Wl,-rpath,$PWD/turtle_amd -o exit_points
@@ -82,6 +84,15 @@ int main(int argc, char * argv[])
         turtle_ecef_to_geodetic_n((long)CAPACITY * N_RAYS, &point[0][0][0], &p_lat[0][0], &p_lon[0][0],
             &p_alt[0][0], TURTLE_AMD_HOST);
 
+        /* the normal of the surface each ray crossed first: the top of layer min(media) */
+        static double normal[N_RAYS][3];
+        static int first_layer[N_RAYS], normal_data[N_RAYS];
+        for (r = 0; r < N_RAYS; r++)
+                first_layer[r] = (n_crossings[r] == 0) ? -1 : /* (an empty slot reads {0, 0}) */
+                    ((media[0][r][0] < media[0][r][1]) ? media[0][r][0] : media[0][r][1]);
+        turtle_stepper_normal_n(stepper, N_RAYS, &point[0][0][0], first_layer, &normal[0][0], normal_data,
+            TURTLE_AMD_HOST);
+
         int through_rock = 0;
         for (r = 0; r < N_RAYS; r++) {
                 const int kept = (n_crossings[r] < CAPACITY) ? n_crossings[r] : CAPACITY;
@@ -98,7 +109,12 @@ int main(int argc, char * argv[])
                         printf(" exit %.9f %.9f %.4f", p_lat[exit][r], p_lon[exit][r], p_alt[exit][r]);
                 else
                         printf(" exit none");
-                printf(" span %.3f m\n", (exit > entry) ? distance[exit][r] - distance[entry][r] : 0.);
+                printf(" span %.3f m", (exit > entry) ? distance[exit][r] - distance[entry][r] : 0.);
+                if (normal_data[r] >= 0)
+                        printf(" first crossing cosine %.6f\n", direction[r][0] * normal[r][0] +
+                                direction[r][1] * normal[r][1] + direction[r][2] * normal[r][2]);
+                else
+                        printf(" first crossing cosine none\n");
         }
         printf("%d lines of sight, %d through rock\n", N_RAYS, through_rock);
 

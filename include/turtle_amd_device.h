@@ -36,7 +36,8 @@
  *   Stepping   the library's own idiom: trip() evaluates exactly one sample per live lane,
  *              whatever the ray is doing, and reports events.  k_walk's and k_traverse's
  *              inner block, lifted out.
- * and isotropic(), the Philox direction of turtle_amd_isotropic_n / turtle_stepper_scatter_n.
+ * and isotropic(), the Philox direction of turtle_amd_isotropic_n / turtle_stepper_scatter_n,
+ * and normal(), one point of turtle_stepper_normal_n: the normal of the surface a ray crossed.
  *
  * What the functions assume: wave64, and trip() called from converged code (it predicates on
  * `live` itself).  They use no LDS, no global state and no atomics.  Paging is not offered on
@@ -924,6 +925,11 @@ __device__ __forceinline__ bool d_grid_elevation(
 /* [ref map.c:280-378], as it is -- including the slip at map.c:352-353: for a
  * point in the grid's first half-row (iy == 0, hy <= 0.5) the y-gradient lands
  * in gx and gy is left untouched.  gx, gy are therefore in-out. */
+/* SELECTS: which of gx, gy the first half-row writes is said with selects on the two values.
+ * (Written as the reference's branches, the compiler merges the two stores into one store
+ * through a selected ADDRESS, and gx, gy then live in scratch memory: 24 bytes a lane in
+ * k_gradient, whose instruction stream is kept as it is.)  Same values either way. */
+template <bool SELECTS = false>
 __device__ __forceinline__ bool d_grid_gradient(
     const tamd_grid & g, double x, double y, double & gx, double & gy)
 {
@@ -969,7 +975,17 @@ __device__ __forceinline__ bool d_grid_gradient(
         }
         if (hy <= 0.5) { /* [ref map.c:350-361] */
                 const double gy1 = (z01 - z00) * (1. - hx) + (z11 - z10) * hx;
-                if (iy == 0) {
+                if (SELECTS) {
+                        double q = gy1;
+                        if (iy != 0) {
+                                const double z0_1 = d_node(g, ix, iy - 1), z1_1 = d_node(g, ix + 1, iy - 1);
+                                const double gy0 = (z00 - z0_1) * (1. - hx) + (z10 - z1_1) * hx;
+                                const double ay = hy + 0.5;
+                                q = gy0 * (1. - ay) + gy1 * ay;
+                        }
+                        q = q / g.dy;
+                        gx = (iy == 0) ? q : gx, gy = (iy == 0) ? gy : q;
+                } else if (iy == 0) {
                         gx = gy1 / g.dy; /* sic [ref map.c:353] */
                 } else {
                         const double z0_1 = d_node(g, ix, iy - 1), z1_1 = d_node(g, ix + 1, iy - 1);
@@ -1573,7 +1589,9 @@ template <int MODE, int MATH>
 struct Geometry {
         tamd_view v;
         OneCtx ctx;
-        __device__ __forceinline__ explicit Geometry(const turtle_amd_view & view) : v(view.geometry)
+        __device__ __forceinline__ explicit Geometry(const turtle_amd_view & view) : Geometry(view.geometry) {}
+        /* (the library's own kernels take the tables bare) */
+        __device__ __forceinline__ explicit Geometry(const tamd_view & geometry) : v(geometry)
         {
                 ctx.slots = nullptr; /* (the LDS table of tile pointers is the library's kernels' own) */
                 if (MODE != GENERIC) {
@@ -1660,6 +1678,148 @@ __device__ __forceinline__ bool step(const Geometry<MODE, MATH> & g, State & st,
         st.index[0] = s.m, st.index[1] = s.k;
         st.step_length = taken;
         return true;
+}
+
+/* ---- the normal of a layer's top surface (turtle_stepper_normal_n) ---------- */
+
+/* the step of the central differences that carry a projected map's gradient (metres per map
+ * metre) over to degrees: d(x, y) / d(latitude, longitude) of the forward projection */
+constexpr double kNormalDelta = 1e-3;
+
+/* Elevation and gradient (per degree; 0 on entry) of one data of a layer: 1 inside, 0 outside
+ * (z, glat, glon are then meaningless), kTileFault with `f` filled in.  PROJECTED: the data may
+ * be a projected map (the generic instance alone: d_project is out of line). */
+template <bool PROJECTED>
+__device__ __forceinline__ int d_source_slope(const tamd_view & v, const tamd_meta & mt, double latitude,
+    double longitude, double & z, double & glat, double & glon, TileFault & f)
+{
+        glat = glon = 0.;
+        if (mt.kind == TAMD_FLAT) {
+                z = 0.;
+                return 1;
+        }
+        if (mt.kind == TAMD_MAP) {
+                const tamd_grid & g = v.grids[mt.src];
+                if (PROJECTED && (g.proj.type >= 0)) {
+                        double x, y, gx = 0., gy = 0.;
+                        d_project(g.proj, latitude, longitude, x, y);
+                        if (!d_grid_elevation(g, x, y, z)) return 0;
+                        d_grid_gradient<true>(g, x, y, gx, gy);
+                        /* the chain rule, in this operand order (turtle_amd.h states it) */
+                        const double d = kNormalDelta;
+                        double xp, yp, xm, ym;
+                        d_project(g.proj, latitude + d, longitude, xp, yp);
+                        d_project(g.proj, latitude - d, longitude, xm, ym);
+                        glat = gx * (xp - xm) / (2. * d) + gy * (yp - ym) / (2. * d);
+                        d_project(g.proj, latitude, longitude + d, xp, yp);
+                        d_project(g.proj, latitude, longitude - d, xm, ym);
+                        glon = gx * (xp - xm) / (2. * d) + gy * (yp - ym) / (2. * d);
+                        return 1;
+                }
+                if (!d_grid_elevation(g, longitude, latitude, z)) return 0;
+                d_grid_gradient<true>(g, longitude, latitude, glon, glat);
+                return 1;
+        }
+        /* a stack: the tile that answers for the elevation answers for the gradient
+         * [ref stack.c:338-388]; x = longitude, y = latitude */
+        const int tile = d_stack_tile(v, v.stacks[mt.src], latitude, longitude, f);
+        if (tile < 0) return (tile == kTileFault) ? kTileFault : 0;
+        const tamd_grid & g = v.grids[tile];
+        if (!d_grid_elevation(g, longitude, latitude, z)) return 0;
+        d_grid_gradient<true>(g, longitude, latitude, glon, glat);
+        return 1;
+}
+
+/* The unit normal, towards increasing altitude, of the surface (latitude, longitude) ->
+ * from_geodetic(latitude, longitude, hs(latitude, longitude)) where its height is hs and its
+ * slopes are glat, glon per degree.  Its tangents are A E + glon U and B N + glat U, with (E, N,
+ * U) the local east, north, up [ref ecef.c:136-154] and A, B the metres per degree of longitude
+ * and latitude at that height.  pole: no east term (there is no east at a pole). */
+__device__ __forceinline__ void d_surface_normal(double latitude, double longitude, double hs, double glat,
+    double glon, bool pole, double n[3])
+{
+        const double lambda = longitude * kPi / 180.;
+        const double phi = latitude * kPi / 180.;
+        const double sl = sin(lambda), cl = cos(lambda);
+        const double sp = sin(phi), cp = cos(phi);
+        const double e[3] = { -sl, cl, 0. };
+        const double nn[3] = { -cl * sp, -sl * sp, cp };
+        const double u[3] = { cl * cp, sl * cp, sp };
+        const double g = 1. - kE * kE * sp * sp;
+        const double Rn = kA / sqrt(g);
+        const double Rm = Rn * (1. - kE * kE) / g;
+        const double A = (Rn + hs) * cp * kPi / 180.;
+        const double B = (Rm + hs) * kPi / 180.;
+        const double a = glon / A, b = glat / B;
+        double w[3];
+        for (int i = 0; i < 3; i++) w[i] = pole ? u[i] - b * nn[i] : u[i] - a * e[i] - b * nn[i];
+        const double norm = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+        for (int i = 0; i < 3; i++) n[i] = w[i] / norm;
+}
+
+/* The normal of the top surface of `layer` above or below `pos`, whatever the altitude of `pos`:
+ * one point of turtle_stepper_normal_n (turtle_amd.h has the definition as a loop).  Returns the
+ * rank of the data that answered within the layer, last added first, with n[] set; or -1, n[]
+ * untouched, where the layer has no data (or there is no such layer).  After an event of
+ * Stepping::trip() that crossed from medium a to medium b, the surface crossed is the top of layer
+ * min(a, b).  The arithmetic is always the STRICT one, whatever MATH is.  `fault`: the library's
+ * own kernels over paged stacks (kTileFault comes back, *fault filled in); a view names resident
+ * tiles only. */
+template <int MODE, int MATH>
+__device__ __forceinline__ int normal(const Geometry<MODE, MATH> & g, const double pos[3], int layer,
+    double n[3], TileFault * fault = nullptr)
+{
+        double latitude, longitude, altitude;
+        d_to_geodetic(pos[0], pos[1], pos[2], latitude, longitude, altitude);
+        const bool pole = (pos[0] == 0.) && (pos[1] == 0.); /* [ref ecef.c:77-84] */
+        if ((layer < 0) || (layer >= g.v.n_layers)) return -1;
+
+        TileFault f = { -1, 0, 0 };
+        double z = 0., glat = 0., glon = 0., hs = 0.;
+        int found = -1;
+        if (MODE == ONE_MAP) {
+                if (!d_grid_elevation(g.ctx.grid, longitude, latitude, z)) return -1;
+                d_grid_gradient<true>(g.ctx.grid, longitude, latitude, glon, glat);
+                hs = z + g.ctx.offset;
+                found = 0;
+        } else if (MODE == ONE_STACK) {
+                const int tile = d_stack_tile(g.v, g.ctx.stack, latitude, longitude, f);
+                if (tile == kTileFault) {
+                        if (fault != nullptr) *fault = f;
+                        return kTileFault;
+                }
+                if (tile < 0) return -1;
+                const tamd_grid & t = g.v.grids[tile];
+                if (!d_grid_elevation(t, longitude, latitude, z)) return -1;
+                d_grid_gradient<true>(t, longitude, latitude, glon, glat);
+                hs = z + g.ctx.offset;
+                found = 0;
+        } else {
+                const int end = g.v.layer_first[layer + 1];
+                int di = 0;
+                for (int j = g.v.layer_first[layer]; j < end; j++, di++) { /* [ref stepper.c:897-921] */
+                        const tamd_meta mt = g.v.metas[j];
+                        const int in = d_source_slope<true>(g.v, mt, latitude, longitude, z, glat, glon, f);
+                        if (in == kTileFault) {
+                                if (fault != nullptr) *fault = f;
+                                return kTileFault;
+                        }
+                        if (in == 0) continue;
+                        hs = z + mt.offset;
+                        found = di;
+                        break;
+                }
+                if (found < 0) return -1;
+                if (g.v.geoid >= 0) { /* [ref stepper.c:905-914]: the undulation lifts and tilts the surface */
+                        const tamd_grid & geoid = g.v.grids[g.v.geoid];
+                        const double lo = (longitude >= 0) ? longitude : longitude + 360.;
+                        double undulation, ugx = 0., ugy = 0.;
+                        if (d_grid_elevation(geoid, lo, latitude, undulation)) hs += undulation;
+                        if (d_grid_gradient<true>(geoid, lo, latitude, ugx, ugy)) glon += ugx, glat += ugy;
+                }
+        }
+        d_surface_normal(latitude, longitude, hs, glat, glon, pole, n);
+        return found;
 }
 
 /* what a trip() reports */

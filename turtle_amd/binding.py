@@ -543,6 +543,44 @@ class Stepper:
                                                _ptr(h), layer, _ptr(pos), _ptr(di), sp))
         return pos, di
 
+    def normal(self, position, layer, out=None):
+        """turtle_stepper_normal_n -> (normal, data_index): the unit normal, towards increasing
+        altitude, of the top surface of layer[r] above or below position[r].  `layer` is an int
+        or one per point.  Rows with no data there (data_index -1: no such layer among them)
+        keep what `out` held (zeros without one)."""
+        sp = _space_of(position, layer)
+        pos = _as(position, sp).reshape(-1, 3)
+        n = pos.shape[0]
+        if np.isscalar(layer):
+            lay = _new((n,), sp, np.int32, like=pos)
+            lay[...] = int(layer)
+        else:
+            lay = _as(layer, sp, np.int32).reshape(-1)
+        nrm = out if out is not None else _new((n, 3), sp, like=pos, zero=True)
+        di = _new((n,), sp, np.int32, like=pos)
+        _check(lib().turtle_stepper_normal_n(self.h, C.c_long(n), _ptr(pos), _ptr(lay),
+                                             _ptr(nrm), _ptr(di), sp))
+        return nrm, di
+
+    @staticmethod
+    def crossing_layers(media):
+        """The layer whose top surface each crossing lies on: min(media[..., 0], media[..., 1])
+        of crossings()'s (capacity, n, 2) pairs, flattened slot-major to (capacity * n,).  A ray
+        that left the data, {m, -1}, gives -1 (no layer: normal() reports data_index -1); an
+        EMPTY slot {0, 0} gives layer 0, so mask the slots by n_crossings."""
+        m = media.reshape(-1, 2)
+        if _is_torch(m):
+            import torch
+            return torch.minimum(m[:, 0], m[:, 1]).contiguous()
+        return np.minimum(m[:, 0], m[:, 1])
+
+    def normal_at_crossings(self, point, media):
+        """normal() at the crossings crossings() recorded: `point` (capacity, n, 3) and `media`
+        (capacity, n, 2) -> normal (capacity, n, 3), data_index (capacity, n).  Empty slots
+        (c >= n_crossings[r]) are evaluated as layer 0 at the origin of coordinates: mask them."""
+        nrm, di = self.normal(point.reshape(-1, 3), self.crossing_layers(media))
+        return nrm.reshape(point.shape), di.reshape(point.shape[:-1])
+
     def step(self, position, direction=None, resume=None, outputs=True):
         """turtle_stepper_step_n.  `position` is updated IN PLACE when it
         already is a contiguous float64 array/tensor.  `resume` = the dict a

@@ -22,6 +22,7 @@
  *   k_ecef_*        batch ECEF transforms              [ref ecef.c:41-207]
  *   k_elevation     batch bilinear lookup, map/stack   [ref map.c:229-277, stack.c:300-361]
  *   k_position      batch turtle_stepper_position      [ref stepper.c:877-931]
+ *   k_normal        batch normals of a layer's top surface (turtle_stepper_normal_n)
  *   k_step          batch turtle_stepper_step [ref stepper.c:780-875]: the sample and
  *   k_step_fast     the tentative step; rays that crossed a boundary are listed
  *                   (k_step_fast: the fast-math body of the one-map / one-stack
@@ -316,6 +317,33 @@ __global__ void k_position(tamd_view v, long n, const double * __restrict__ lat,
                                         d_from_geodetic(la, lo, elevation + height[r], x, y, z);
                                         pos[3 * r] = x, pos[3 * r + 1] = y, pos[3 * r + 2] = z;
                                 }
+                        }
+                }
+                if (pg.faulted != nullptr) page_fault(pg, fault, r);
+        }
+}
+
+/* turtle_stepper_normal_n: the normal of the top of layer[r] above or below pos[r], one point per
+ * lane; the arithmetic is normal()'s of turtle_amd_device.h, always the strict one.  A point with
+ * no data there (or no such layer) gets data_index -1 and keeps its row of `out`. */
+template <int MODE>
+__global__ void __launch_bounds__(256) k_normal(tamd_view v, long n, const double * __restrict__ pos,
+    const int * __restrict__ layer, double * __restrict__ out, int * __restrict__ data_index, Paging pg)
+{
+        const Geometry<MODE, STRICT> geo(v);
+        PAGED_ITEMS(pg, n, i0, r)
+        {
+                TileFault fault = { -1, 0, 0 };
+                if (r >= 0) {
+                        const double p[3] = { pos[3 * r], pos[3 * r + 1], pos[3 * r + 2] };
+                        double w[3];
+                        TileFault f = { -1, 0, 0 };
+                        const int found = normal(geo, p, layer[r], w, &f);
+                        if (found == kTileFault) {
+                                fault = f;
+                        } else {
+                                data_index[r] = found;
+                                if (found >= 0) out[3 * r] = w[0], out[3 * r + 1] = w[1], out[3 * r + 2] = w[2];
                         }
                 }
                 if (pg.faulted != nullptr) page_fault(pg, fault, r);
@@ -2577,6 +2605,15 @@ extern "C" int tamd_k_position(struct tamd_view view, long n, const double * lat
 {
         return launch_items("k_position", k_position, n, 0, view, n, lat, lon, height, layer, pos,
             data_index, pg);
+}
+
+extern "C" int tamd_k_normal(struct tamd_view view, long n, const double * pos, const int * layer,
+    double * normal, int * data_index, struct tamd_paging pg)
+{
+        return with_mode(view.mode, [&](auto mode) {
+                return launch_items("k_normal", k_normal<decltype(mode)::value>, n, 0, view, n, pos, layer,
+                    normal, data_index, pg);
+        });
 }
 
 /* n single steps: the step kernel, then -- with a direction and scratch for

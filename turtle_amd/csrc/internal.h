@@ -108,6 +108,10 @@ int tamd_k_gradient(struct tamd_view view, long n, const double * a,
 int tamd_k_position(struct tamd_view view, long n, const double * lat,
     const double * lon, const double * height, int layer, double * pos,
     int * data_index, struct tamd_paging pg);
+/* the unit normal of the top surface of layer[r] at pos[r] (turtle_stepper_normal_n): rows of
+ * `normal` with no data there, or no such layer, are left untouched, their data_index -1 */
+int tamd_k_normal(struct tamd_view view, long n, const double * pos, const int * layer,
+    double * normal, int * data_index, struct tamd_paging pg);
 int tamd_k_step(struct tamd_view view, long n, double * pos,
     const double * dir, double * lat, double * lon, double * alt,
     double * elev, double * step, int * index, int flags, struct tamd_paging pg);

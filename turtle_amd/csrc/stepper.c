@@ -749,6 +749,40 @@ enum turtle_return turtle_stepper_position_n(struct turtle_stepper * stepper, lo
         return TURTLE_RETURN_SUCCESS;
 }
 
+struct normal_args {
+        long n;
+        void *pos, *layer, *normal, *index;
+};
+
+static int normal_round(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
+{
+        struct normal_args * a = p;
+        (void)round;
+        return tamd_k_normal(stepper->view, a->n, a->pos, a->layer, a->normal, a->index, pg);
+}
+
+enum turtle_return turtle_stepper_normal_n(struct turtle_stepper * stepper, long n,
+    const double * position, const int * layer, double * normal, int * data_index, int space)
+{
+        TAMD_ERROR_INIT(&turtle_stepper_normal_n);
+        if ((stepper == NULL) || (position == NULL) || (layer == NULL) || (normal == NULL) ||
+            (data_index == NULL))
+                return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
+        if (n <= 0) return TURTLE_RETURN_SUCCESS;
+        struct tamd_stage st = { 0 };
+        struct normal_args args = { n, NULL, NULL, NULL, NULL };
+        const size_t nb = (size_t)n * sizeof(double);
+        tamd_stage_add(&st, position, 3 * nb, TAMD_IN, &args.pos);
+        tamd_stage_add(&st, layer, n * sizeof(int), TAMD_IN, &args.layer);
+        tamd_stage_add(&st, normal, 3 * nb, TAMD_INOUT, &args.normal); /* untouched rows keep their value */
+        tamd_stage_add(&st, data_index, n * sizeof(int), TAMD_OUT, &args.index);
+        if (tamd_stage_open(&st, space)) return TAMD_RAISE_DEVICE();
+        const int rc = stepper_rounds(stepper, n, &normal_round, &args);
+        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
+        if (tamd_stage_close(&st)) return TAMD_RAISE_DEVICE();
+        return TURTLE_RETURN_SUCCESS;
+}
+
 /* Grow-only scratch of the batch calls: 4 n ints (the rays a trace hands from
  * pass to pass, the rays whose step crossed a boundary and what they found
  * there / the rays a batch of steps defers to its bisection pass; the step
