@@ -424,6 +424,57 @@ TURTLE_API enum turtle_return turtle_map_resample(struct turtle_map * map,
     struct turtle_stack * stack /* or NULL */, const struct turtle_map * source /* or NULL */,
     int flags, long * outside /* or NULL */, long * clamped /* or NULL */);
 
+/* Flags of turtle_map_fill_n. */
+enum turtle_amd_fill_flags {
+        /* an elevation outside the map's span is stored as the nearest end of the span
+         * instead of failing the call (TURTLE_AMD_RESAMPLE_CLAMP's rule) */
+        TURTLE_AMD_FILL_CLAMP = 1
+};
+
+/* Writes the window of nx x ny nodes whose south-west corner is node (ix0, iy0) from rows of
+ * doubles: a numpy array, or a tensor already on the GPU, becomes a map without a file or a
+ * call per node.  It is exactly this loop, done all or nothing:
+ *
+ *     for (j = 0; j < ny; j++) for (i = 0; i < nx; i++)
+ *             turtle_map_fill(map, ix0 + i, iy0 + j, elevation[j * ld + i]);
+ *
+ * Row j of the array is map row iy0 + j, SOUTH TO NORTH, as turtle_map_node counts iy (an
+ * image that has north first is flipped by its owner); ld >= nx is the distance between two
+ * rows, in doubles, so a window of a wider array is passed as it lies.  Every stored code is
+ * the one turtle_map_fill stores, signed (hgt) maps included.  The departures from the loop:
+ * 1. if any element fails turtle_map_fill's checks the call fails with DOMAIN_ERROR and that
+ * function's message ("inconsistent elevation value", "elevation is outside of map span"),
+ * NO node changes, on the host or in any HBM copy, and *clamped is left alone; 2. a NaN,
+ * which the scalar call lets through to an undefined cast, always fails, with "elevation is
+ * outside of map span"; 3. with TURTLE_AMD_FILL_CLAMP an off-span value is stored as the
+ * nearest end of the span (z0 when dz <= 0) and counted in *clamped; a NaN still fails.
+ * BAD_ADDRESS: map or elevation is NULL; DOMAIN_ERROR: unknown flags, an unknown space, a map
+ * that is a tile of a stack, a window that is not inside the map ("point is outside of map"),
+ * ld < nx -- all raised before the device is touched, and changing nothing.  nx <= 0 or
+ * ny <= 0 does nothing and succeeds.  Afterwards every reader sees the new nodes:
+ * turtle_map_node / _dump and the host path, the kernels, and steppers that hold the map
+ * already; copies on other devices go stale.  Both spaces run the same kernels (HOST rows go
+ * through HBM: the (ny - 1) * ld + nx doubles they span), and the call has completed when it
+ * returns, in either space.  The work follows the window, not the map: a patch of a large
+ * map that is on the device moves the patch.  A map in use by another thread is the caller's
+ * race, as with turtle_map_fill.  clamped: may be NULL. */
+TURTLE_API enum turtle_return turtle_map_fill_n(struct turtle_map * map, int ix0, int iy0,
+    int nx, int ny, const double * elevation /* [ny][ld] */, long ld, int flags,
+    long * clamped /* or NULL */, int space);
+
+/* Reads the same window: elevation[j * ld + i] is the value that
+ *
+ *     turtle_map_node(map, ix0 + i, iy0 + j, NULL, NULL, &z)
+ *
+ * returns, bit for bit, signed maps included; row j of the array is map row iy0 + j, south
+ * to north.  The departures: the elements between the rows (ld > nx) are not touched; the
+ * node coordinates are not returned (they are x0 + ix * dx, y0 + iy * dy of turtle_map_meta);
+ * the values come from the map's HBM copy, through a kernel, in either space, and in DEVICE
+ * space the call is asynchronous as the other batch calls are.  Errors as for
+ * turtle_map_fill_n, without the flags; a tile of a stack can be read. */
+TURTLE_API enum turtle_return turtle_map_node_n(const struct turtle_map * map, int ix0, int iy0,
+    int nx, int ny, double * elevation /* [ny][ld] */, long ld, int space);
+
 /* n gradients (the surface normal a Monte-Carlo needs at a hit point).  The
  * output arrays are in-out, as in the scalar calls. */
 TURTLE_API enum turtle_return turtle_map_gradient_n(
@@ -609,7 +660,7 @@ TURTLE_API enum turtle_return turtle_stepper_trace_n(
  * FINISHED before the release.
  * While a thread holds a view, batch calls over resident geometry work as ever (on that
  * stepper too).  What would change the geometry fails in the holding thread with DOMAIN_ERROR
- * instead of waiting for its own view: turtle_map_fill, turtle_map_resample,
+ * instead of waiting for its own view: turtle_map_fill, turtle_map_fill_n, turtle_map_resample,
  * turtle_stack_clear / _load, turtle_map_destroy / turtle_stack_destroy (through the handler;
  * the object stays), a batch call that has to page tiles in, and, on the stepper itself,
  * turtle_stepper_add_* and turtle_stepper_destroy.  Other threads that would change it wait

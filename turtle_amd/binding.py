@@ -19,6 +19,7 @@ STEP_RESUME = 1
 TRACE_RESUME = 1
 SCATTER_START = 1
 RESAMPLE_CLAMP = 1
+FILL_CLAMP = 1
 
 RETURN_NAMES = [
     "SUCCESS", "BAD_ADDRESS", "BAD_EXTENSION", "BAD_FORMAT", "BAD_PROJECTION",
@@ -141,6 +142,38 @@ def _ptr(a):
     if _is_torch(a):
         return C.c_void_p(a.data_ptr())
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _row_stride(a):
+    """The distance between two rows of a 2-D float64 array whose last dimension is contiguous,
+    in elements; 0 if the array is not one the C calls can use where it lies."""
+    if _is_torch(a):
+        import torch
+        if a.dtype != torch.float64:
+            return 0
+        s0, s1 = a.stride()
+    else:
+        if a.dtype != np.float64 or not a.flags.aligned:
+            return 0
+        s0, s1 = (s // 8 if s % 8 == 0 else -1 for s in a.strides)
+    ny, nx = a.shape
+    if nx > 1 and s1 != 1:
+        return 0
+    if ny <= 1:
+        return max(nx, 1)
+    return s0 if s0 >= nx else 0
+
+
+def _rows(a, space):
+    """-> (2-D float64 array in `space`, its row stride): `a` itself when it can be used as it
+    lies, else a contiguous copy"""
+    if not _is_torch(a):
+        a = np.asarray(a)
+    if a.ndim != 2:
+        raise ValueError("a 2-D array is expected")
+    if (space == HOST and _is_torch(a)) or not _row_stride(a):
+        a = _as(a, space)
+    return a, _row_stride(a)
 
 
 # ---- device management ------------------------------------------------------
@@ -391,6 +424,39 @@ class Map:
                                          RESAMPLE_CLAMP if clamp else 0, C.byref(outside),
                                          C.byref(clamped)))
         return outside.value, clamped.value
+
+    def fill_array(self, z, ix0=0, iy0=0, clamp=False):
+        """turtle_map_fill_n: the window whose south-west node is (ix0, iy0) from the 2-D array
+        `z` (rows south to north; numpy, or a torch tensor on the GPU, used where it lies when
+        it is float64 with a contiguous last dimension: a slice of a wider array is not copied)
+        -> the number of values clamped to the span.  All or nothing: a value turtle_map_fill
+        would refuse, or a NaN, raises DOMAIN_ERROR and changes no node."""
+        sp = _space_of(z)
+        z, ld = _rows(z, sp)
+        clamped = C.c_long(0)
+        _check(lib().turtle_map_fill_n(self.h, int(ix0), int(iy0), int(z.shape[1]), int(z.shape[0]),
+                                       _ptr(z), C.c_long(ld), FILL_CLAMP if clamp else 0,
+                                       C.byref(clamped), sp))
+        return clamped.value
+
+    def nodes(self, ix0=0, iy0=0, nx=None, ny=None, device=False, out=None):
+        """turtle_map_node_n: the window's node values as a 2-D float64 array (rows south to
+        north), a numpy array or, with `device`, a torch tensor on the GPU; or into `out`
+        (2-D, contiguous last dimension: its shape is the window, its space decides)."""
+        if out is not None:
+            if out.ndim != 2 or not _row_stride(out):
+                raise ValueError("out: a 2-D float64 array with a contiguous last dimension")
+            sp = _space_of(out)
+            ny, nx = out.shape
+        else:
+            meta = self.meta()
+            nx = meta["nx"] - ix0 if nx is None else nx
+            ny = meta["ny"] - iy0 if ny is None else ny
+            sp = DEVICE if device else HOST
+            out = _new((max(ny, 0), max(nx, 0)), sp)
+        _check(lib().turtle_map_node_n(self.h, int(ix0), int(iy0), int(nx), int(ny), _ptr(out),
+                                       C.c_long(_row_stride(out) or nx), sp))
+        return out
 
     def elevation_scalar(self, x, y, want_inside=True):
         z, inside = C.c_double(-12345.0), C.c_int(-1)

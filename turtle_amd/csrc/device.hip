@@ -2479,6 +2479,76 @@ __global__ void k_unblock(const uint16_t * __restrict__ blocked, int nx, int ny,
         }
 }
 
+/* turtle_map_fill_n, first half: the window's elevations (row j at z + j * ld) to the codes
+ * turtle_map_fill stores, k_resample's expressions in its operand order, into a compact
+ * buffer of ny rows of nx codes.  Nothing of the map is written: the host commits
+ * (k_fill_store) only after it has read counters[0] == 0.  counters (zeroed by the caller):
+ * elements that fail the call, elements clamped, and the failed ones that turtle_map_fill calls
+ * "inconsistent" (dz <= 0 and z != z0; a NaN is not among them). */
+__global__ void __launch_bounds__(256) k_fill_encode(const double * __restrict__ z_in, long ld, int nx, long n,
+    double z0, double dz, int is_signed, int flags, uint16_t * __restrict__ codes, ull * __restrict__ counters)
+{
+        const double top = z0 + 65535 * dz; /* [ref map.c:196-197] */
+        ull n_bad = 0, n_clamped = 0, n_inconsistent = 0;
+        for (long k = blockIdx.x * (long)blockDim.x + threadIdx.x; k < n; k += (long)gridDim.x * blockDim.x) {
+                const long j = k / nx;
+                double z = z_in[j * ld + (k - j * nx)];
+                /* turtle_map_fill [ref map.c:192-200, :47-51]; a NaN passes none of its comparisons */
+                const bool nan = (z != z);
+                const bool off = nan || ((dz <= 0.) && (z != z0)) || (z < z0) || (z > top);
+                uint16_t code = 0;
+                if (off && (nan || !(flags & TURTLE_AMD_FILL_CLAMP))) {
+                        n_bad++, n_inconsistent += (!nan && (dz <= 0.) && (z != z0)) ? 1 : 0;
+                } else {
+                        if (off) {
+                                n_clamped++;
+                                z = ((dz <= 0.) || (z < z0)) ? z0 : top;
+                        }
+                        if (is_signed)
+                                code = (uint16_t)(int)z; /* (int16)z */
+                        else
+                                code = (dz > 0.) ? (uint16_t)(unsigned)round((z - z0) / dz) : 0;
+                }
+                codes[k] = code;
+        }
+        block_tally(counters, n_bad, n_clamped, n_inconsistent, 0);
+}
+
+/* ... second half: the codes into the map's HBM copy, in place.  One wave a touched 8 x 8
+ * block (nwx of them a row of the window), its lanes in HBM order: a lane outside the window
+ * keeps the code that is there (blank: the copy held nothing yet and the window is the whole
+ * map -- the padding of its last blocks is zeroed), and the block goes out as its 128-byte line. */
+__global__ void __launch_bounds__(256) k_fill_store(uint16_t * __restrict__ nodes, int nbx, int ix0, int iy0,
+    int nx, int ny, int nwx, long n_blocks, int blank, const uint16_t * __restrict__ codes)
+{
+        const int lane = (int)(threadIdx.x & 63);
+        const long waves = (long)gridDim.x * (blockDim.x >> 6);
+        for (long i = blockIdx.x * (long)(blockDim.x >> 6) + (threadIdx.x >> 6); i < n_blocks; i += waves) {
+                const int bx = (ix0 >> 3) + (int)(i % nwx), by = (iy0 >> 3) + (int)(i / nwx);
+                const int ix = bx * TAMD_BLOCK + (lane & 7) - ix0, iy = by * TAMD_BLOCK + (lane >> 3) - iy0;
+                const size_t k = ((size_t)by * nbx + bx) * 64 + lane;
+                uint16_t code = 0;
+                if ((ix >= 0) && (ix < nx) && (iy >= 0) && (iy < ny))
+                        code = codes[(long)iy * nx + ix];
+                else if (!blank)
+                        code = GLOBAL_NODES(nodes)[k];
+                nodes[k] = code;
+        }
+}
+
+/* turtle_map_node_n: the window's nodes decoded as turtle_map_node decodes them [ref
+ * map.c:41-44], row j to out + j * ld; consecutive lanes store consecutive doubles */
+__global__ void __launch_bounds__(256) k_nodes(const uint16_t * __restrict__ nodes, int nbx, int ix0, int iy0,
+    int nx, long n, double z0, double dz, int is_signed, double * __restrict__ out, long ld)
+{
+        for (long k = blockIdx.x * (long)blockDim.x + threadIdx.x; k < n; k += (long)gridDim.x * blockDim.x) {
+                const long j = k / nx;
+                const int i = (int)(k - j * nx);
+                const uint16_t code = GLOBAL_NODES(nodes)[d_node_index(nbx, ix0 + i, iy0 + (int)j)];
+                out[j * ld + i] = is_signed ? (double)(int16_t)code : z0 + code * dz;
+        }
+}
+
 } /* namespace */
 
 /* ======================================================================== */
@@ -3192,4 +3262,28 @@ extern "C" int tamd_k_resample(struct tamd_view view, const struct tamd_grid * g
 extern "C" int tamd_k_unblock(const uint16_t * blocked, int nx, int ny, int nbx, uint16_t * rows)
 {
         return launch_items("k_unblock", k_unblock, (long)nx * ny, 0, blocked, nx, ny, nbx, rows);
+}
+
+extern "C" int tamd_k_fill_encode(const double * elevation, long ld, int nx, int ny, double z0, double dz,
+    int is_signed, int flags, uint16_t * codes, unsigned long long * counters)
+{
+        const long n = (long)nx * ny;
+        return launch_items("k_fill_encode", k_fill_encode, n, 0, elevation, ld, nx, n, z0, dz, is_signed, flags,
+            codes, counters);
+}
+
+extern "C" int tamd_k_fill_store(uint16_t * nodes, int nbx, int ix0, int iy0, int nx, int ny, int blank,
+    const uint16_t * codes)
+{
+        const int nwx = ((ix0 + nx - 1) >> 3) - (ix0 >> 3) + 1, nwy = ((iy0 + ny - 1) >> 3) - (iy0 >> 3) + 1;
+        const long n_blocks = (long)nwx * nwy;
+        return launch_items("k_fill_store", k_fill_store, n_blocks * 64, 0, nodes, nbx, ix0, iy0, nx, ny, nwx,
+            n_blocks, blank, codes);
+}
+
+extern "C" int tamd_k_nodes(const uint16_t * nodes, int nbx, int ix0, int iy0, int nx, int ny, double z0,
+    double dz, int is_signed, double * elevation, long ld)
+{
+        const long n = (long)nx * ny;
+        return launch_items("k_nodes", k_nodes, n, 0, nodes, nbx, ix0, iy0, nx, n, z0, dz, is_signed, elevation, ld);
 }

@@ -111,6 +111,8 @@ const char * turtle_error_function(turtle_function_t * caller)
         NAME(turtle_map_elevation_n);
         NAME(turtle_stack_elevation_n);
         NAME(turtle_map_resample);
+        NAME(turtle_map_fill_n);
+        NAME(turtle_map_node_n);
         NAME(turtle_stepper_position_n);
         NAME(turtle_stepper_normal_n);
         NAME(turtle_stepper_step_n);

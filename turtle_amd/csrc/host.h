@@ -102,6 +102,8 @@ void tamd_map_release(struct turtle_map * map);
 int tamd_map_host_nodes(struct turtle_map * map);
 /* fills the decode parameters of `grid` and makes the HBM copy current */
 int tamd_map_sync(struct turtle_map * map, struct tamd_grid * grid);
+/* the same without the upload, for a caller that overwrites the whole copy (map.c) */
+int tamd_map_sync_blank(struct turtle_map * map, struct tamd_grid * grid, int * blank);
 enum turtle_return tamd_map_load_(struct turtle_map ** map, const char * path,
     struct tamd_error * error, const char * file, int line);
 /* Codecs (hgt.c, tiff.c): a header-only probe that fills the meta data, and a
@@ -322,9 +324,11 @@ void tamd_pager_end(struct tamd_pager * pager);
  * A variant of a call is a direction chosen at the declaration, not a second list.  TAMD_TABLE is
  * a host blob of the library's own that the kernels of this call read (a one-grid view): in the
  * arena in either space, and the close then waits in either space, before the arena is reused.
+ * TAMD_SCRATCH is a piece of the arena that belongs to the call alone (`user` is not read: pass
+ * NULL), in either space and copied neither way; the close waits as for a table.
  * At most TAMD_STAGE_ARRAYS declarations; one more makes the open fail.  An error between open
  * and close just returns: nothing is held. */
-enum { TAMD_IN = 1, TAMD_OUT = 2, TAMD_INOUT = 3, TAMD_TABLE = 5 };
+enum { TAMD_IN = 1, TAMD_OUT = 2, TAMD_INOUT = 3, TAMD_TABLE = 5, TAMD_SCRATCH = 8 };
 #define TAMD_STAGE_ARRAYS 12
 struct tamd_stage {
         int n;               /* arrays declared so far: starts from { 0 } */

@@ -221,6 +221,19 @@ int tamd_k_resample(struct tamd_view view, const struct tamd_grid * grids, int f
     struct tamd_paging pg, unsigned long long * counters);
 /* the map's host rows (south to north) from an HBM copy */
 int tamd_k_unblock(const uint16_t * blocked, int nx, int ny, int nbx, uint16_t * rows);
+/* turtle_map_fill_n: the window's elevations (ny rows of nx, `ld` doubles apart) encoded as
+ * turtle_map_fill encodes them into ny x nx codes; nothing of the map is written.  counters: 4 x
+ * uint64 zeroed by the caller -- elements that fail the call (off the span and not clamped, or
+ * NaN), elements clamped, the failed ones with dz <= 0 and z != z0 (not NaN).  flags: enum turtle_amd_fill_flags. */
+int tamd_k_fill_encode(const double * elevation, long ld, int nx, int ny, double z0, double dz,
+    int is_signed, int flags, uint16_t * codes, unsigned long long * counters);
+/* ... and those codes into the window (ix0, iy0, nx, ny) of an HBM copy, in place, a wave a
+ * touched block.  blank: the copy holds nothing yet and the window is the whole map. */
+int tamd_k_fill_store(uint16_t * nodes, int nbx, int ix0, int iy0, int nx, int ny, int blank,
+    const uint16_t * codes);
+/* turtle_map_node_n: the window of an HBM copy decoded into ny rows of nx doubles, `ld` apart */
+int tamd_k_nodes(const uint16_t * nodes, int nbx, int ix0, int iy0, int nx, int ny, double z0,
+    double dz, int is_signed, double * elevation, long ld);
 
 #ifdef __cplusplus
 }

@@ -337,7 +337,24 @@ int tamd_map_host_nodes(struct turtle_map * map)
         return rc;
 }
 
-int tamd_map_sync(struct turtle_map * map, struct tamd_grid * grid)
+static int map_sync(struct turtle_map * map, struct tamd_grid * grid, int upload);
+
+int tamd_map_sync(struct turtle_map * map, struct tamd_grid * grid) { return map_sync(map, grid, 1); }
+
+/* ... for a caller about to overwrite EVERY node of the copy (turtle_map_fill_n over the whole
+ * map): the copy is there, but a stale one is not brought up to date -- *blank says so, and
+ * the copy stays marked stale until the caller has filled it */
+int tamd_map_sync_blank(struct turtle_map * map, struct tamd_grid * grid, int * blank)
+{
+        if (map_sync(map, grid, 0)) return 1;
+        const int device = tamd_dev_current();
+        tamd_geometry_lock();
+        *blank = !(map->d_fresh & (1u << device));
+        tamd_geometry_unlock();
+        return 0;
+}
+
+static int map_sync(struct turtle_map * map, struct tamd_grid * grid, int upload)
 {
         /* HBM layout: blocks of TAMD_BLOCK x TAMD_BLOCK nodes (internal.h); one copy
          * per device, made when a thread on that device first needs it */
@@ -357,7 +374,7 @@ int tamd_map_sync(struct turtle_map * map, struct tamd_grid * grid)
                 }
                 map->d_fresh &= ~(1u << device);
         }
-        if (!(map->d_fresh & (1u << device))) {
+        if (upload && !(map->d_fresh & (1u << device))) {
                 int failed;
                 if (map->staged != NULL) {
                         /* a tile just read: laid out already, in page-locked memory

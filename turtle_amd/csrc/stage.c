@@ -39,9 +39,11 @@ void tamd_stage_add(struct tamd_stage * st, const void * user, size_t bytes, int
         st->n++;
 }
 
-/* does the array have a piece of the arena?  (a table has one in either space) */
+/* does the array have a piece of the arena?  (a table has one in either space, and so has a
+ * scratch piece, which has no array of the user's behind it) */
 static int staged(const struct tamd_stage * st, const struct tamd_stage_array * a)
 {
+        if (a->dir == TAMD_SCRATCH) return 1;
         return (a->user != NULL) && ((st->space != TURTLE_AMD_DEVICE) || (a->dir == TAMD_TABLE));
 }
 
