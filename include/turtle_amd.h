@@ -551,6 +551,55 @@ TURTLE_API enum turtle_return turtle_stepper_normal_n(
     const int * layer /* [n] */, double * normal /* [n][3], in / out */,
     int * data_index /* [n], mandatory */, int space);
 
+/* The skyline around n observers: for each of n_azimuths directions, how high the top of a layer
+ * stands against the sky, the maximum over n_distances samples of the line -- what decides the
+ * open-sky acceptance of a muography telescope, or whether an antenna on the ground sees a shower.
+ * Item i = r * n_azimuths + a is line a of observer r; the outputs are observer-major, an
+ * observer's profile contiguous.  `azimuth` (degrees) and `distance` (metres along the observer's
+ * horizontal) are shared by all observers and live in the same memory space as the other arrays.
+ * For every item, exactly this, with the reference's functions:
+ *
+ *     turtle_ecef_to_geodetic(p = position[r], &lat0, &lon0, &alt0);           (alt0 is not used)
+ *     (E, N, U) = east, north, up at (lat0, lon0)     [the frame of turtle_ecef_from_horizontal]
+ *     turtle_ecef_from_horizontal(lat0, lon0, azimuth[a], 0., h);  (the horizontal unit vector)
+ *     best = -HUGE_VAL;  best_k = 0;
+ *     for (k = 0; k < n_distances; k++) {
+ *             s = distance[k];  q[j] = p[j] + s * h[j];              (a product, then a sum)
+ *             turtle_ecef_to_geodetic(q, &la, &lo, &al);                      (al is not used)
+ *             turtle_stepper_position(stepper, la, lo, 0., layer_index, g, &di);
+ *             if (di < 0) continue;                (no data there: reported by omission, never raised)
+ *             d = g - p;  rr = d0*d0 + d1*d1 + d2*d2;
+ *             if (rr <= FLT_EPSILON) continue;               [turtle_ecef_to_horizontal's own test]
+ *             arg = (U0*d0 + U1*d1 + U2*d2) / sqrt(rr);        (the sine of the elevation angle)
+ *             if (arg > best) { best = arg; best_k = k + 1; best_range = sqrt(rr); }
+ *     }
+ *     sample[i] = best_k;                             (0: no sample of the line had data)
+ *     if (best_k) { elevation[i] = best > 1. ? 90. : best < -1. ? -90. : asin(best) * 180. / M_PI;
+ *                   if (range) range[i] = best_range; }       (else both keep their values)
+ *
+ * The choice is made on the sine, and asin is taken once, of the winner: the angle's maximum,
+ * without near-vertical values collapsing into ties.  Ties go to the smallest k.  A NaN never wins
+ * (a NaN distance gives one).  A sample at the observer's own foot (distance 0 from an observer
+ * that turtle_stepper_position_n placed at height 0) is skipped by the rr test.  The arithmetic of
+ * the selection is the strict one, as in turtle_stepper_position_n; only the two
+ * turtle_ecef_to_geodetic transforms honour turtle_amd_math_set, as turtle_ecef_to_geodetic_n does.
+ *
+ * BAD_ADDRESS: stepper, position, azimuth, distance, elevation or sample NULL (range may be).
+ * DOMAIN_ERROR: layer_index outside the stepper's layers ("no valid data"), an unknown space,
+ * n * n_azimuths beyond an int.  n, n_azimuths or n_distances <= 0 does nothing and succeeds.
+ * A wave cannot wait for a tile in the middle of its reduction, so every tile of every stack has
+ * to be in memory, as for turtle_amd_stepper_view_acquire: the call loads what is missing
+ * (turtle_stack_load) and fails with DOMAIN_ERROR where a stack's stack_size is below its number
+ * of tiles.  turtle_amd_stepper_rounds reports 1 afterwards.  In DEVICE space the call only queues
+ * work. */
+TURTLE_API enum turtle_return turtle_stepper_horizon_n(
+    struct turtle_stepper * stepper, long n, const double * position /* [n][3] */,
+    int n_azimuths, const double * azimuth /* [n_azimuths], degrees */,
+    int n_distances, const double * distance /* [n_distances], metres */,
+    int layer_index, double * elevation /* [n][n_azimuths], in / out */,
+    int * sample /* [n][n_azimuths], mandatory */,
+    double * range /* [n][n_azimuths] or NULL */, int space);
+
 /* Flags of turtle_stepper_step_n. */
 enum turtle_amd_step_flags {
         /* On entry altitude[], elevation[][2] and index[][2] hold the values a

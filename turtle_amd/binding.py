@@ -647,6 +647,31 @@ class Stepper:
         nrm, di = self.normal(point.reshape(-1, 3), self.crossing_layers(media))
         return nrm.reshape(point.shape), di.reshape(point.shape[:-1])
 
+    def horizon(self, position, azimuth, distance, layer=0, out=None, want=("range",)):
+        """turtle_stepper_horizon_n -> dict(elevation, sample[, range]), each (n, n_az): for every
+        observer and azimuth (degrees) the elevation angle (degrees) of the highest of the line's
+        samples of the top of `layer`, taken at the horizontal distances `distance` (metres), the
+        1-based number of that sample and its range (metres).  Lines without a sample that has
+        data get sample 0 and keep what `out` held (a prefilled elevation, or a dict of a prefilled
+        "elevation" and / or "range"), zeros without one."""
+        sp = _space_of(position, azimuth, distance)
+        pos = _as(position, sp).reshape(-1, 3)
+        az, ds = _as(azimuth, sp).reshape(-1), _as(distance, sp).reshape(-1)
+        n, n_az, n_d = pos.shape[0], az.shape[0], ds.shape[0]
+        given = out if isinstance(out, dict) else dict(elevation=out)
+        el, rng = given.get("elevation"), given.get("range")
+        if el is None:
+            el = _new((n, n_az), sp, like=pos, zero=True)
+        if rng is None and "range" in want:
+            rng = _new((n, n_az), sp, like=pos, zero=True)
+        smp = _new((n, n_az), sp, np.int32, like=pos, zero=True)
+        _check(lib().turtle_stepper_horizon_n(self.h, C.c_long(n), _ptr(pos), n_az, _ptr(az), n_d, _ptr(ds),
+                                              layer, _ptr(el), _ptr(smp), _ptr(rng), sp))
+        res = dict(elevation=el, sample=smp)
+        if rng is not None:
+            res["range"] = rng
+        return res
+
     def step(self, position, direction=None, resume=None, outputs=True):
         """turtle_stepper_step_n.  `position` is updated IN PLACE when it
         already is a contiguous float64 array/tensor.  `resume` = the dict a

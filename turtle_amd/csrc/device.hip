@@ -23,6 +23,8 @@
  *   k_elevation     batch bilinear lookup, map/stack   [ref map.c:229-277, stack.c:300-361]
  *   k_position      batch turtle_stepper_position      [ref stepper.c:877-931]
  *   k_normal        batch normals of a layer's top surface (turtle_stepper_normal_n)
+ *   k_horizon       the skyline around observers, one wave per line of sight: the highest of a
+ *                   line's samples of a layer's top (turtle_stepper_horizon_n)
  *   k_step          batch turtle_stepper_step [ref stepper.c:780-875]: the sample and
  *   k_step_fast     the tentative step; rays that crossed a boundary are listed
  *                   (k_step_fast: the fast-math body of the one-map / one-stack
@@ -347,6 +349,117 @@ __global__ void __launch_bounds__(256) k_normal(tamd_view v, long n, const doubl
                         }
                 }
                 if (pg.faulted != nullptr) page_fault(pg, fault, r);
+        }
+}
+
+/* The top of `layer` under (la, lo) as turtle_stepper_position finds it [ref stepper.c:892-914]:
+ * the layer's data last added first, the offset, the geoid -- k_position's arithmetic, always the
+ * strict one.  false where no data answers; a tile that is not resident answers nothing (the
+ * callers run over resident geometry). */
+template <int MODE>
+__device__ __forceinline__ bool d_layer_top(const tamd_view & v, const OneCtx & ctx, int layer, double la,
+    double lo, double & elevation)
+{
+        TileFault f;
+        if (MODE == TAMD_MODE_ONE_MAP) {
+                if (!d_grid_elevation<false>(ctx.grid, lo, la, elevation)) return false;
+                elevation += ctx.offset;
+                return true;
+        }
+        if (MODE == TAMD_MODE_ONE_STACK) {
+                if (d_stack_elevation<false>(v, ctx.stack, la, lo, elevation, f) <= 0) return false;
+                elevation += ctx.offset;
+                return true;
+        }
+        const int end = v.layer_first[layer + 1];
+        for (int j = v.layer_first[layer]; j < end; j++) {
+                const tamd_meta mt = v.metas[j];
+                const int in = d_source_elevation(v, mt, la, lo, elevation, f);
+                if (in < 0) return false;
+                if (in == 0) continue;
+                elevation += mt.offset;
+                if (v.geoid >= 0) {
+                        double undulation;
+                        const double l360 = (lo >= 0) ? lo : lo + 360.;
+                        if (d_grid_elevation(v.grids[v.geoid], l360, la, undulation)) elevation += undulation;
+                }
+                return true;
+        }
+        return false;
+}
+
+/* turtle_stepper_horizon_n: the skyline around observers.  One WAVE per item i = r * n_az + a
+ * (line a of observer r), four items a block; lane l takes the samples k = l, l + 64, ... of the
+ * line and keeps its own best (sine of the elevation angle, k + 1, range); the wave then reduces
+ * the 64 triples with a butterfly of shuffles under the order "larger sine, then smaller k", which
+ * is what the strict `>` of the sequential loop gives, and lane 0 writes.  The observer's preamble
+ * (its geodetic coordinates, the frame, the horizontal unit vector) is wave-uniform and computed by
+ * every lane.  FAST: the two to_geodetic transforms only; everything else is the strict
+ * arithmetic.  No paging: the geometry is resident. */
+template <int MODE, bool FAST>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_horizon(tamd_view v, int n_items, int n_az, int n_d,
+    const double * __restrict__ pos, const double * __restrict__ azimuth,
+    const double * __restrict__ distance, int layer, double * __restrict__ elevation,
+    int * __restrict__ sample, double * __restrict__ range)
+{
+        OneCtx ctx;
+        d_load_ctx<MODE, false>(v, ctx);
+        const int lane = (int)(threadIdx.x & 63);
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        for (long i = blockIdx.x * 4L + wave; i < (long)n_items; i += (long)gridDim.x * 4L) {
+                const long r = i / n_az;
+                const int a = (int)(i - r * n_az);
+                const double p0 = pos[3 * r], p1 = pos[3 * r + 1], p2 = pos[3 * r + 2];
+                double lat0, lon0, alt0;
+                if (FAST)
+                        f_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
+                else
+                        d_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
+                double e[3], nn[3], u[3], h[3];
+                d_enu(lat0, lon0, e, nn, u);
+                { /* turtle_ecef_from_horizontal at elevation 0 [ref ecef.c:160-176] */
+                        const double az = azimuth[a] * kPi / 180.;
+                        const double el = 0. * kPi / 180.;
+                        const double ce = cos(el);
+                        const double q0 = ce * sin(az), q1 = ce * cos(az), q2 = sin(el);
+                        for (int j = 0; j < 3; j++) h[j] = q0 * e[j] + q1 * nn[j] + q2 * u[j];
+                }
+
+                double best = -HUGE_VAL, best_range = 0.;
+                int best_k = 0;
+                for (int k = lane; k < n_d; k += 64) {
+                        const double s = distance[k];
+                        const double x = p0 + s * h[0], y = p1 + s * h[1], z = p2 + s * h[2];
+                        double la, lo, al, top;
+                        if (FAST)
+                                f_to_geodetic(x, y, z, la, lo, al);
+                        else
+                                d_to_geodetic(x, y, z, la, lo, al);
+                        if (!d_layer_top<MODE>(v, ctx, layer, la, lo, top)) continue;
+                        double g0, g1, g2;
+                        d_from_geodetic(la, lo, top + 0., g0, g1, g2);
+                        const double d0 = g0 - p0, d1 = g1 - p1, d2 = g2 - p2;
+                        double rr = d0 * d0 + d1 * d1 + d2 * d2;
+                        if (rr <= FLT_EPSILON) continue; /* [ref ecef.c:194] */
+                        rr = sqrt(rr);
+                        const double arg = (u[0] * d0 + u[1] * d1 + u[2] * d2) / rr;
+                        if (arg > best) best = arg, best_k = k + 1, best_range = rr; /* (a NaN never wins) */
+                }
+                for (int off = 32; off > 0; off >>= 1) {
+                        const double o_best = __shfl_xor(best, off, 64);
+                        const double o_range = __shfl_xor(best_range, off, 64);
+                        const int o_k = __shfl_xor(best_k, off, 64);
+                        /* (a lane without a sample holds (-inf, 0): it never wins, and loses to any) */
+                        if ((o_best > best) || ((o_best == best) && (o_k != 0) && (o_k < best_k)))
+                                best = o_best, best_k = o_k, best_range = o_range;
+                }
+                if (lane == 0) {
+                        sample[i] = best_k;
+                        if (best_k != 0) {
+                                elevation[i] = (best > 1.) ? 90. : ((best < -1.) ? -90. : asin(best) * 180. / kPi);
+                                if (range != nullptr) range[i] = best_range;
+                        }
+                }
         }
 }
 
@@ -2683,6 +2796,22 @@ extern "C" int tamd_k_normal(struct tamd_view view, long n, const double * pos, 
         return with_mode(view.mode, [&](auto mode) {
                 return launch_items("k_normal", k_normal<decltype(mode)::value>, n, 0, view, n, pos, layer,
                     normal, data_index, pg);
+        });
+}
+
+/* n_items = observers x azimuths lines, one wave each, four to a block */
+extern "C" int tamd_k_horizon(struct tamd_view view, int n_items, int n_azimuths, int n_distances,
+    const double * pos, const double * azimuth, const double * distance, int layer, double * elevation,
+    int * sample, double * range)
+{
+        if (tamd_dev_init()) return 1;
+        if ((n_items <= 0) || (n_azimuths <= 0) || (n_distances <= 0)) return 0;
+        return with_mode(view.mode, [&](auto mode) {
+                return with_math(g_math_strict, [&](auto fast) {
+                        return launch_blocks("k_horizon", k_horizon<decltype(mode)::value, decltype(fast)::value>,
+                            grid_for(64L * n_items, 256), 0, view, n_items, n_azimuths, n_distances, pos, azimuth,
+                            distance, layer, elevation, sample, range);
+                });
         });
 }
 

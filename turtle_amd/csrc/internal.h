@@ -112,6 +112,12 @@ int tamd_k_position(struct tamd_view view, long n, const double * lat,
  * `normal` with no data there, or no such layer, are left untouched, their data_index -1 */
 int tamd_k_normal(struct tamd_view view, long n, const double * pos, const int * layer,
     double * normal, int * data_index, struct tamd_paging pg);
+/* the skyline (turtle_stepper_horizon_n): item r * n_azimuths + a is line a of observer r; over
+ * RESIDENT geometry only (a tile that is not in memory answers nothing); items without a sample
+ * that has data get sample 0 and keep their elevation and range (NULL: not wanted) */
+int tamd_k_horizon(struct tamd_view view, int n_items, int n_azimuths, int n_distances,
+    const double * pos, const double * azimuth, const double * distance, int layer, double * elevation,
+    int * sample, double * range);
 int tamd_k_step(struct tamd_view view, long n, double * pos,
     const double * dir, double * lat, double * lon, double * alt,
     double * elev, double * step, int * index, int flags, struct tamd_paging pg);
