@@ -509,6 +509,25 @@ struct CrossList {
                          * packed (cross_pack); batches of single steps: NULL */
 };
 
+/* A trace's list of crossings in two parts, so that the lined pass's own waves can locate the
+ * first while its long rays go on (trace_body, "the crossings under the tail"): L1, the front
+ * of the arrays, counted by CrossList.count -- phase A's crossings and what a wave of the lined
+ * pass lists until it learns that the queue is dry; L2, the same arrays from the far end, counted
+ * by l2_count -- what it lists from then on.  n_dry counts the waves that have learnt it: once it
+ * equals the waves of the grid nobody adds to L1 any more, and a wave that has run out of rays
+ * locates L1 by tickets of 64 entries drawn from l1_next.  k_cross takes the rest.  NULL: one
+ * list, all of it left to k_cross. */
+constexpr int kQ = 16; /* words between two counters of a trace: see run_trace */
+constexpr int kQTail = 4 * kQ;
+struct CrossTail {
+        ull * words; /* the three counters, kQ words apart */
+        /* (the lined pass finds them kQTail words behind its queue's counter and is told by a flag
+         * to look: TRACE_CROSS_TAIL -- its kernel has no register to spare for a pointer) */
+        __device__ __forceinline__ ull * n_dry() const { return words; }
+        __device__ __forceinline__ ull * l1_next() const { return words + kQ; }
+        __device__ __forceinline__ ull * l2_count() const { return words + 2 * kQ; }
+};
+
 /* (medium, data index) of a sample, each -1 .. 65 534, in one int */
 __device__ __forceinline__ int cross_pack(int m, int k) { return (m + 1) | ((k + 1) << 16); }
 __device__ __forceinline__ void cross_unpack(int packed, int & m, int & k)
@@ -842,7 +861,9 @@ enum { ST_INIT = 0, ST_STEP = 1, ST_BISECT = 2 };
  * the output is deterministic. */
 /* TRACE_CARRY_MEDIUM: the caller knows which medium each ray is in (a trace
  * resumed after a boundary, or after parking) */
-enum { TRACE_CARRY_MEDIUM = 1 };
+/* TRACE_CROSS_TAIL (the fast lined pass over resident data): the crossings go to two lists, and
+ * the pass's own waves locate the first (CrossTail) */
+enum { TRACE_CARRY_MEDIUM = 1, TRACE_CROSS_TAIL = 2 };
 
 /* ---- a workgroup's pool of rays in LDS (round 4) --------------------------
  *
@@ -979,7 +1000,28 @@ struct PhaseIO {
  * position, the medium it left, path length and step count in the ray arrays;
  * its id, the tentative length and the medium the sample found in ph.cross -- and
  * k_cross locates every crossing of the batch afterwards, in full waves.  The
- * lane takes a new ray at once. */
+ * lane takes a new ray at once.
+ *
+ * The crossings under the tail (TAIL: the fast lined pass over resident data; CrossTail).  The
+ * lined pass's queue is dry after a third of the pass and the rest of it is ever fewer waves with
+ * the batch's longest rays, while the crossings -- packed, independent work -- waited for the last
+ * of them.  A wave that has run out of rays now locates them before it leaves, if it can know that
+ * the list it reads is complete: a wave lists into L1 until it learns that the queue is dry (from
+ * its own refill, or from a look at the queue's counter every kTailPeek general iterations), then
+ * releases what it has written, adds one to n_dry and lists into L2 from then on.  n_dry == the
+ * waves of the grid therefore says that L1 and the rays on it are final and visible to whoever
+ * reads n_dry and then acquires.  A wave that finds less leaves as it always did: nothing waits
+ * for another wave, and a block that starts late makes the count complete later, never wrongly.
+ * The locating waves run one priority level below the tracing ones, so that a long ray's wave on
+ * the same SIMD issues first.  The same statements on the same values as k_cross (cross_locate),
+ * the same additions to the totals: which kernel located a crossing changes no bit. */
+constexpr int kTailPeek = 16;
+template <int MODE, bool FAST, bool PAGED>
+__device__ __forceinline__ void cross_locate(const tamd_view & v, const OneCtx & ctx, double * __restrict__ pos,
+    const double * __restrict__ dir, int * __restrict__ index, double * __restrict__ length,
+    int * __restrict__ n_steps, const CrossList & cross, const Paging & pg, const RayOut & out, long first,
+    long stride, int lane, long hi, ull & my_rays, ull & my_samples);
+
 template <int MODE, bool FAST, bool MODEL, bool PAGED, bool CROSS, bool POOL = false>
 __device__ __forceinline__ void trace_body(const tamd_view & v, long n,
     double * __restrict__ pos, const double * __restrict__ dir, int max_steps,
@@ -1011,9 +1053,17 @@ __device__ __forceinline__ void trace_body(const tamd_view & v, long n,
         int creep_wait = 0;                /* wave-uniform: general iterations before a busy wave tries lean steps again */
         int relay_wait = 0;                /* general iterations that lanes of a busy wave have waited for a closed form */
         bool exhausted = false;            /* wave-uniform */
+        /* (not the pooled instances: with the locating inlined they need 20 and 12 bytes more scratch a lane) */
+        constexpr bool TAIL = MODEL && CROSS && FAST && !PAGED && !POOL &&
+            ((MODE == TAMD_MODE_ONE_MAP) || (MODE == TAMD_MODE_ONE_STACK));
+        int tail_peek = 0;                 /* wave-uniform, TAIL: general iterations since the last look at the
+                                            * queue; -1 once the wave has added itself to n_dry */
         OneCtx ctx;
         d_load_ctx<MODE, FAST>(v, ctx);
         CellCache cell = { ~0u, 0u, 0u, -1, nullptr };
+        const CrossTail tail = { queue + kQTail };
+        if constexpr (TAIL)
+                if (flags & TRACE_CROSS_TAIL) __builtin_amdgcn_s_setprio(1);
 
         long ray = -1;
         bool dead = false;
@@ -1241,6 +1291,31 @@ __device__ __forceinline__ void trace_body(const tamd_view & v, long n,
                                 }
                         }
                         pool_next += min((long)__popcll(mask), avail);
+                }
+                /* ---- TAIL: the moment the wave learns that the queue is dry (once) ---- */
+                if constexpr (TAIL) {
+                        if ((flags & TRACE_CROSS_TAIL) && (tail_peek >= 0)) {
+                                /* (wave-uniform, and the compiler is told so: the counter stays scalar) */
+                                bool dry = __builtin_amdgcn_readfirstlane((int)exhausted) != 0;
+                                if (!dry && (++tail_peek >= kTailPeek)) {
+                                        /* (a wave that holds its rays never asks the queue) */
+                                        tail_peek = 0;
+                                        const ull drawn = __hip_atomic_load(queue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                        dry = __builtin_amdgcn_readfirstlane((int)(drawn >= (ull)n)) != 0;
+                                }
+                                if (dry) {
+                                        /* what the wave listed into L1, and those rays' state: released
+                                         * BEFORE the add that says so (the wait: the fence's own may be
+                                         * dropped where the compiler thinks nothing is in flight) */
+                                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                                        if ((threadIdx.x & 63) == 0)
+                                                __hip_atomic_fetch_add(tail.n_dry(), 1ull, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT);
+                                        tail_peek = -1;
+                                }
+                        }
                 }
                 if (__ballot(ray >= 0) == 0) {
                         if (!(POOLED && pooled)) break;
@@ -1763,14 +1838,18 @@ __device__ __forceinline__ void trace_body(const tamd_view & v, long n,
                         if (cmask != 0) {
                                 const int leader = __builtin_ctzll(cmask);
                                 ull base = 0;
+                                /* (TAIL: L2, from the far end, once the wave has said that it lists
+                                 * no more into L1 -- a ray crosses once: the two never meet) */
+                                const bool far = TAIL && (tail_peek < 0);
                                 if ((int)(threadIdx.x & 63) == leader)
-                                        base = atomicAdd(ph.cross.count, (ull)__popcll(cmask));
+                                        base = atomicAdd(far ? tail.l2_count() : ph.cross.count, (ull)__popcll(cmask));
                                 base = __shfl(base, leader, 64);
                                 if (crossed) {
                                         const int rank = lane_rank(cmask);
-                                        ph.cross.ray[base + rank] = (int)ray;
-                                        ph.cross.ds[base + rank] = ds;
-                                        ph.cross.other[base + rank] = cross_pack(bm, bk);
+                                        const long place = far ? capacity - 1 - (long)(base + rank) : (long)(base + rank);
+                                        ph.cross.ray[place] = (int)ray;
+                                        ph.cross.ds[place] = ds;
+                                        ph.cross.other[place] = cross_pack(bm, bk);
                                         /* B is the tentative point; m, k the medium it left */
                                         pos[3 * ray] = bx, pos[3 * ray + 1] = by, pos[3 * ray + 2] = bz;
                                         index[2 * ray] = m, index[2 * ray + 1] = k;
@@ -1808,6 +1887,33 @@ __device__ __forceinline__ void trace_body(const tamd_view & v, long n,
                 for (int i = 0; i < 24; i++)
                         if (pstat_[i]) atomicAdd(&g_pool_stats[i], pstat_[i]);
 #endif
+        /* ---- TAIL: the wave has no ray left: if L1 is final it locates L1's crossings ---- */
+        if constexpr (TAIL) {
+                if (flags & TRACE_CROSS_TAIL) {
+                        const int lane = (int)(threadIdx.x & 63);
+                        const ull n_dry = __hip_atomic_load(tail.n_dry(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (__builtin_amdgcn_readfirstlane((int)(n_dry == (ull)gridDim.x * 4) /* blocks of four waves */) != 0) {
+                                /* one acquire, ahead of the first load of anything handed over: the
+                                 * list's entries and the listed rays' position, medium, length, steps */
+                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                                __builtin_amdgcn_s_setprio(0);
+                                const ull l1_ = __hip_atomic_load(ph.cross.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                const long l1 = (long)__shfl(l1_, 0, 64);
+                                for (;;) {
+                                        ull ticket = 0;
+                                        if (lane == 0) ticket = atomicAdd(tail.l1_next(), 64ull);
+                                        ticket = __shfl(ticket, 0, 64);
+                                        if ((long)ticket >= l1) break;
+                                        ull got_rays = 0, got_samples = 0;
+                                        cross_locate<MODE, true, false>(v, ctx, pos, dir, index, length, n_steps, ph.cross,
+                                            ph.pg, ph.out, (long)ticket, 64, lane, min((long)ticket + 64, l1), got_rays,
+                                            got_samples);
+                                        /* (k_cross's additions: a crossing is a ray and a step) */
+                                        my_rays += got_rays, my_steps += got_rays, my_samples += got_samples;
+                                }
+                        }
+                }
+        }
         block_tally(stats, my_rays, my_steps, my_samples, my_capped);
 }
 
@@ -1896,18 +2002,19 @@ k_trace(tamd_view v, long n,
  * boundary within 1e-9 m of q) the trace kernel's word stands, so that a listed
  * ray always ends here.  A ray that needs a tile which is not resident goes back
  * before its step and on the pager's list, as in k_trace. */
+/* The entries [lo, hi) of the list: the caller's lanes take entry i0 + lane of each round i0 = first,
+ * first + stride, ... (whole waves go round: page_fault).  k_cross calls it, a block a round, and
+ * so does the lined pass, a wave a ticket (see CrossTail). */
 template <int MODE, bool FAST, bool PAGED>
-__global__ void __launch_bounds__(256) k_cross(tamd_view v, double * __restrict__ pos,
+__device__ __forceinline__ void cross_locate(const tamd_view & v, const OneCtx & ctx, double * __restrict__ pos,
     const double * __restrict__ dir, int * __restrict__ index, double * __restrict__ length,
-    int * __restrict__ n_steps, CrossList cross, Paging pg, ull * __restrict__ stats, RayOut out)
+    int * __restrict__ n_steps, const CrossList & cross, const Paging & pg, const RayOut & out, long first,
+    long stride, int lane, long hi, ull & my_rays, ull & my_samples)
 {
         constexpr bool CAN_FAULT = PAGED && (MODE != TAMD_MODE_ONE_MAP);
-        OneCtx ctx;
-        d_load_ctx<MODE, FAST>(v, ctx);
-        const long n = (long)*cross.count;
-        ull my_rays = 0, my_samples = 0;
-        for (long i0 = blockIdx.x * (long)blockDim.x; i0 < n; i0 += (long)gridDim.x * blockDim.x) {
-                const long i = i0 + threadIdx.x; /* whole waves go round (page_fault) */
+        const long n = hi;
+        for (long i0 = first; i0 < n; i0 += stride) {
+                const long i = i0 + lane;
                 TileFault fault = { -1, 0, 0 };
                 int home = -1;
                 long r = -1;
@@ -1994,6 +2101,30 @@ __global__ void __launch_bounds__(256) k_cross(tamd_view v, double * __restrict_
                         }
                 }
                 if (CAN_FAULT && (pg.faulted != nullptr)) page_fault(pg, fault, r, home);
+        }
+}
+
+/* What the lined pass left: of the list's front (see CrossTail) the entries from `front.l1_next` on --
+ * all of it where no lined pass located any (front.words NULL) -- and the entries at its far end,
+ * front.l2_count of them below `capacity`. */
+template <int MODE, bool FAST, bool PAGED>
+__global__ void __launch_bounds__(256) k_cross(tamd_view v, double * __restrict__ pos,
+    const double * __restrict__ dir, int * __restrict__ index, double * __restrict__ length,
+    int * __restrict__ n_steps, CrossList cross, Paging pg, ull * __restrict__ stats, RayOut out,
+    CrossTail front, long capacity)
+{
+        OneCtx ctx;
+        d_load_ctx<MODE, FAST>(v, ctx);
+        const long n = (long)*cross.count;
+        const long done = (front.words != nullptr) ? min((long)*front.l1_next(), n) : 0;
+        const long n_back = (front.words != nullptr) ? (long)*front.l2_count() : 0;
+        const long first = blockIdx.x * (long)blockDim.x, stride = (long)gridDim.x * blockDim.x;
+        ull my_rays = 0, my_samples = 0;
+#pragma unroll 1
+        for (int part = 0; part < 2; part++) { /* (one copy of the body) */
+                const long lo = (part == 0) ? done : capacity - n_back, hi = (part == 0) ? n : capacity;
+                cross_locate<MODE, FAST, PAGED>(v, ctx, pos, dir, index, length, n_steps, cross, pg, out, lo + first,
+                    stride, (int)threadIdx.x, hi, my_rays, my_samples);
         }
         block_tally(stats, my_rays, my_rays, my_samples, 0);
 }
@@ -2934,13 +3065,13 @@ static int launch_trace(struct tamd_view view, long n, bool n_on_device, double 
 template <int MODE, bool FAST>
 static int launch_cross(struct tamd_view view, long n, double * pos, const double * dir, int * index,
     double * length, int * n_steps, CrossList cross, Paging pg, ull * stats,
-    RayOut out = { nullptr, nullptr, nullptr, nullptr, nullptr })
+    RayOut out = { nullptr, nullptr, nullptr, nullptr, nullptr }, CrossTail front = { nullptr })
 {
         constexpr bool CAN_PAGE = (MODE != TAMD_MODE_ONE_MAP);
         const bool paged = CAN_PAGE && (pg.faulted != nullptr);
         const auto kernel = paged ? k_cross<MODE, FAST, CAN_PAGE> : k_cross<MODE, FAST, false>;
         return launch_blocks("k_cross", kernel, persistent_blocks(kernel, n), 0, view, pos, dir, index, length,
-            n_steps, cross, pg, stats, out);
+            n_steps, cross, pg, stats, out, front, n);
 }
 
 /* ---- the launch policy ---------------------------------------------------
@@ -3041,6 +3172,27 @@ static int spatial_order(int mode, long n)
          * 5.95, 11.17 -> 10.92, 26.7 -> 26.3 ms; a 4 x 4 stack at 1 / 10 M rays 4.10 -> 4.10, 25.5 -> 22.8) */
         return n >= ((value > 1) ? value : 3000000L);
 }
+/* Do the lined pass's own waves locate the crossings that were listed before its queue ran dry
+ * (CrossTail; trace_body, "the crossings under the tail")?  The same bits either way
+ * (tests/test_gpu_cross_tail.py).  Measured, one MI355X, off -> on, a pass in ms.  One batch at a
+ * time: one map at 1 / 2 / 4 / 6 M rays 3.23-3.28 -> 3.11-3.19, 5.90-5.92 -> 5.75-5.79, 11.09-11.18 ->
+ * 10.89-11.41, 13.69-13.78 -> 13.39-13.67; a 4 x 4 stack at 1 / 3 M rays 4.20-4.33 -> 4.21-4.22, 10.98-11.14
+ * -> 10.85; but C3 (10 M, a stack) 22.6 -> 25.7 and C4 (12.5 M, one map, pooled kernel with the
+ * code in) 25.9 -> 26.4: k_cross all but vanishes (2.7 -> 0.04 ms, 2.9 -> 0.05) and the lined pass
+ * grows by more (14.9 -> 21.7, 16.5 -> 20.2 ms) -- the long rays' chains slow down beside locating
+ * waves on their SIMD, a priority level below them or not, for as long as the list lasts, and a
+ * large batch's list lasts for milliseconds.  Three batches in flight: the tail is not idle then
+ * (the next batch's bulk fills it) and the locating only competes: 1 / 2 / 4 M rays 2.19-2.21 ->
+ * 2.26-2.27, 3.95 -> 4.38-4.41, 8.03-8.10 -> 9.41-9.69.  So: one batch at a time, up to 3 M rays.
+ * TURTLE_AMD_CROSS_TAIL=0 / 1: never (one list, all of it left to k_cross) / wherever the kernel
+ * has the code. */
+static int cross_tail_on(long n)
+{
+        static Knob knob = { "TURTLE_AMD_CROSS_TAIL", -1 };
+        const long value = knob.get();
+        if (value >= 0) return value != 0;
+        return (g_ctx.in_flight <= 1) && (n <= 3000000L);
+}
 /* phase A hands over when its queue is dry and a wave is down to this many rays (PhaseIO.drain_lanes;
  * 0: never, as in the passes that have nobody to hand over to): 64, so any wave does */
 constexpr int kDrainLanes = 64;
@@ -3066,7 +3218,6 @@ static char * sort_room_of(int * parked, long n)
  * 6.9-7.8 ms against 6.0 ms.)
  * Without scratch for the lists (`parked` NULL: a batch beyond 2^31 rays) there
  * is one pass, which bisects in place. */
-constexpr int kQ = 16; /* words between two counters of a trace: see run_trace */
 template <int MODE>
 static int run_trace(struct tamd_view view, long n, double * pos, const double * dir,
     int max_steps, int * index, double * length, int * n_steps, int flags, int * parked,
@@ -3081,7 +3232,9 @@ static int run_trace(struct tamd_view view, long n, double * pos, const double *
         /* lists: parked[0 .. n) from A to B (from both ends), parked[n .. 3n) the crossings;
          * counters, kQ words (a cache line or two) apart -- every wave of a pass adds to them:
          * queue[0], [kQ]: the work queues of A, B; queue[2 kQ], [3 kQ]: the lengths of the lists;
-         * queue[4 kQ]: of the first list's far end */
+         * queue[4 kQ]: of the first list's far end; queue[5 kQ], [6 kQ], [7 kQ]: the lined pass's waves
+         * that know their queue dry, the tickets drawn on the crossings' list and the length of that
+         * list's far end (CrossTail) */
         const bool listed = (parked != nullptr) && (cross_ds != nullptr) && (length != nullptr) &&
             (n_steps != nullptr);
         const CrossList none = { nullptr, nullptr, nullptr, nullptr };
@@ -3109,6 +3262,11 @@ static int run_trace(struct tamd_view view, long n, double * pos, const double *
         PhaseIO b = { parked, queue + 2 * kQ, nullptr, nullptr, 0, 1, pg, 0, park, kChunk,
                 creep_lanes(n), dense_go(), cross };
         b.pool = pool_on(MODE, n);
+        /* (the lined pass's instances that have the code: fast, one map or one stack, nothing paged) */
+        CrossTail tail = { nullptr };
+        if ((MODE != TAMD_MODE_GENERIC) && (pg.faulted == nullptr) && cross_tail_on(n))
+                tail.words = queue + 1 * kQ + kQTail; /* (behind the lined pass's queue: see CrossTail) */
+        const int tail_flag = (tail.words != nullptr) ? TRACE_CROSS_TAIL : 0;
         const int long_if = sort_long_if();
         if (!again && (long_if > 0)) {
                 /* (a later round of a paged trace takes rays at any step count: unsorted) */
@@ -3191,12 +3349,12 @@ static int run_trace(struct tamd_view view, long n, double * pos, const double *
                 b.ids = ids.Current();
         }
         if (launch_trace<MODE, true, true>(view, n, true, pos, dir, max_steps, index, length,
-                n_steps, flags | TRACE_CARRY_MEDIUM, b, stats, queue + 1 * kQ))
+                n_steps, flags | TRACE_CARRY_MEDIUM | tail_flag, b, stats, queue + 1 * kQ))
                 return 1;
-        return launch_cross<MODE, true>(view, n, pos, dir, index, length, n_steps, cross, pg, stats, out);
+        return launch_cross<MODE, true>(view, n, pos, dir, index, length, n_steps, cross, pg, stats, out, tail);
 }
 
-/* queue: five counters (see run_trace); parked: room for 3 n ray ids and cross_ds
+/* queue: eight counters (see run_trace); parked: room for 3 n ray ids and cross_ds
  * for 3 n doubles (the lists of the passes; what the hand-over sorts by in the last n),
  * or NULL.  pg: the round of a paged
  * geometry (paging.c), all NULL otherwise; the counters in `stats` add up over the
@@ -3217,7 +3375,7 @@ extern "C" int tamd_k_trace(struct tamd_view view, long n, double * pos,
                 return 1;
         }
         if (pg.ids == nullptr) HIP_TRY(hipMemsetAsync(stats, 0, 4 * sizeof(ull), g_stream));
-        HIP_TRY(hipMemsetAsync(queue, 0, 5 * kQ * sizeof(ull), g_stream));
+        HIP_TRY(hipMemsetAsync(queue, 0, 8 * kQ * sizeof(ull), g_stream));
         if (n <= 0) return 0;
         const int carry = ((flags & TURTLE_AMD_TRACE_RESUME) ? TRACE_CARRY_MEDIUM : 0) |
             ((parked != nullptr) ? (flags & TAMD_TRACE_SORT_ROOM) : 0);

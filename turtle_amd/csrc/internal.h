@@ -131,7 +131,7 @@ int tamd_k_step(struct tamd_view view, long n, double * pos,
  * `parked` has room for TAMD_TRACE_SORT_INTS x n ints and TAMD_TRACE_SORT_TEMP
  * bytes more behind them: the hand-over list is then ORDERED before the lined
  * pass reads it (run_trace in device.hip). */
-#define TAMD_TRACE_COUNTERS 96
+#define TAMD_TRACE_COUNTERS 128
 #define TAMD_TRACE_SORT_ROOM 0x100
 /* a flag of the step kernels beside enum turtle_amd_step_flags: `alt` holds the tentative length
  * of the next step instead of the altitude, `elev` is not used (turtle_stepper_walk_n) */
