@@ -605,7 +605,10 @@ enum turtle_amd_step_flags {
         /* On entry altitude[], elevation[][2] and index[][2] hold the values a
          * previous call returned for the SAME positions: skip the sample at
          * the start point, exactly as the reference's `last` cache does when
-         * the position is unchanged [impl stepper.c:708-710, :745-748]. */
+         * the position is unchanged [impl stepper.c:708-710, :745-748].  A ray
+         * handed back with index[r][0] = -1 has left the data and takes no step
+         * (step[r] = 0), whatever a fresh sample of the point where its exit
+         * was located, within 1e-8 m of the rim, would say. */
         TURTLE_AMD_STEP_RESUME = 1
 };
 

@@ -595,6 +595,12 @@ __device__ __forceinline__ void step_items(const tamd_view & v, long n,
                         my_samples++;
                         fault = s.fault;
                         home = s.slot;
+                        /* a ray handed back as having left the data has left it, as the
+                         * reference's cache would answer [ref stepper.c:708-710, :791-796]: it
+                         * stands within the 1e-8 m of the bisection that located its exit, where
+                         * an ulp of the fast transform can tell this sample otherwise -- and the
+                         * ray would walk back in */
+                        if ((flags & TURTLE_AMD_STEP_RESUME) && directed && (fault.centre < 0)) s.m = -1, s.k = -1;
                 }
 
                 double ds = 0.;
