@@ -600,6 +600,64 @@ TURTLE_API enum turtle_return turtle_stepper_horizon_n(
     int * sample /* [n][n_azimuths], mandatory */,
     double * range /* [n][n_azimuths] or NULL */, int space);
 
+/* The polar viewshed around n observers: which of the samples along the lines of
+ * turtle_stepper_horizon_n the observer SEES -- which slopes the lines of sight of a muography
+ * telescope enter first, which ground an antenna is in view of, and from which range on a target
+ * `target_height` metres above the ground comes into view.  Items, observers, azimuths, distances,
+ * the observer's frame (E, N, U) and the horizontal unit vector h are exactly those of
+ * turtle_stepper_horizon_n; the distances are swept in the order they are given (increasing, for
+ * a viewshed).  The outputs are [n][n_azimuths][n_distances], a line's samples contiguous:
+ * element e = (long)i * n_distances + k.  For every item i, after horizon_n's preamble:
+ *
+ *     best = -HUGE_VAL;  count = 0;
+ *     for (k = 0; k < n_distances; k++) {
+ *             s = distance[k];  q[j] = p[j] + s * h[j];  turtle_ecef_to_geodetic(q, &la, &lo, &al);
+ *             turtle_stepper_position(stepper, la, lo, 0., layer_index, g, &di);
+ *             skip = (di < 0);                                              (no data there)
+ *             if (!skip) { d = g - p;  rr = d0*d0 + d1*d1 + d2*d2;  skip = (rr <= FLT_EPSILON);
+ *                          ground = (U0*d0 + U1*d1 + U2*d2) / sqrt(rr); }
+ *             if (!skip) {
+ *                     if (target_height == 0.) target = ground;
+ *                     else { turtle_stepper_position(stepper, la, lo, target_height, layer_index, t, &di);
+ *                            d = t - p;  rr = d0*d0 + d1*d1 + d2*d2;  skip = (rr <= FLT_EPSILON);
+ *                            target = (U0*d0 + U1*d1 + U2*d2) / sqrt(rr); }
+ *             }
+ *             if (horizon) horizon[e] = best;    (the maximum of the GROUND sines of the samples before k)
+ *             if (skip) { visible[e] = -1;  if (sine) sine[e] = NAN;  continue; }
+ *             if (sine) sine[e] = target;
+ *             v = (target >= best);              (a NaN is never visible; grazing counts as seen)
+ *             visible[e] = v;  count += v;
+ *             if (ground > best) best = ground;  (a NaN never raises the horizon)
+ *     }
+ *     if (n_visible) n_visible[i] = count;
+ *
+ * Every element of every output that is given is written: they are OUT only, nothing is read from
+ * them.  The first sample with data is visible, behind a horizon of -HUGE_VAL.  A skipped sample
+ * (-1) neither is seen nor hides anything.  The arithmetic is the strict one; only the
+ * turtle_ecef_to_geodetic transforms honour turtle_amd_math_set, as in turtle_stepper_horizon_n --
+ * and of a sample's transform only latitude and altitude: its longitude is the closed form's
+ * atan2 in either arithmetic.  A line due north or south of an observer on a whole degree runs
+ * along a seam of the tiles, where the last ulp of the longitude says which tile answers and,
+ * beside a missing tile, whether a sample has data at all; those flags are the reference's too.
+ * A maximum rounds nothing: whatever the order the samples of a line are combined in on the
+ * device, horizon[] is the running maximum of the ground's sines to the bit.
+ *
+ * BAD_ADDRESS: stepper, position, azimuth, distance or visible NULL (sine, horizon and n_visible
+ * may be).  DOMAIN_ERROR: layer_index outside the stepper's layers ("no valid data"), an unknown
+ * space, n * n_azimuths beyond an int.  n, n_azimuths or n_distances <= 0 does nothing and
+ * succeeds.  Every tile of every stack has to be in memory, as for turtle_stepper_horizon_n: the
+ * call loads what is missing and fails with DOMAIN_ERROR where a stack's stack_size is below its
+ * number of tiles; turtle_amd_stepper_rounds reports 1 afterwards.  In DEVICE space the call only
+ * queues work. */
+TURTLE_API enum turtle_return turtle_stepper_viewshed_n(
+    struct turtle_stepper * stepper, long n, const double * position /* [n][3] */,
+    int n_azimuths, const double * azimuth /* [n_azimuths], degrees */,
+    int n_distances, const double * distance /* [n_distances], metres, in the order they are swept */,
+    int layer_index, double target_height /* metres above the layer's top */,
+    signed char * visible /* [n][n_azimuths][n_distances], mandatory */,
+    double * sine /* same shape, or NULL */, double * horizon /* same shape, or NULL */,
+    int * n_visible /* [n][n_azimuths], or NULL */, int space);
+
 /* Flags of turtle_stepper_step_n. */
 enum turtle_amd_step_flags {
         /* On entry altitude[], elevation[][2] and index[][2] hold the values a

@@ -130,7 +130,7 @@ def _new(shape, space, dtype=np.float64, like=None, zero=False):
     if space == DEVICE:
         import torch
         tdt = torch.float64 if dtype == np.float64 else (
-            torch.int32 if dtype == np.int32 else torch.int64)
+            torch.int32 if dtype == np.int32 else torch.int8 if dtype == np.int8 else torch.int64)
         dev = like.device if (like is not None and _is_torch(like)) else "cuda"
         return (torch.zeros if zero else torch.empty)(shape, dtype=tdt, device=dev)
     return (np.zeros if zero else np.empty)(shape, dtype=dtype)
@@ -670,6 +670,29 @@ class Stepper:
         res = dict(elevation=el, sample=smp)
         if rng is not None:
             res["range"] = rng
+        return res
+
+    def viewshed(self, position, azimuth, distance, layer=0, target_height=0.0,
+                 want=("sine", "horizon", "n_visible")):
+        """turtle_stepper_viewshed_n -> dict(visible int8 (n, n_az, n_d)[, sine, horizon (the same
+        shape), n_visible int32 (n, n_az)]): along the lines of `horizon`, swept in the order of
+        `distance`, whether the observer sees a target `target_height` metres above the top of
+        `layer` at each sample (1, 0, or -1 where the sample has no data or is the observer's own
+        foot), the sine of the target's elevation angle (NaN where -1), the largest sine of the
+        ground before the sample (-inf: none yet) and the number of samples seen on each line."""
+        sp = _space_of(position, azimuth, distance)
+        pos = _as(position, sp).reshape(-1, 3)
+        az, ds = _as(azimuth, sp).reshape(-1), _as(distance, sp).reshape(-1)
+        n, n_az, n_d = pos.shape[0], az.shape[0], ds.shape[0]
+        res = dict(visible=_new((n, n_az, n_d), sp, np.int8, like=pos))     # (the call writes every element
+        for name in ("sine", "horizon"):                                    # of each: nothing to clear)
+            if name in want:
+                res[name] = _new((n, n_az, n_d), sp, like=pos)
+        if "n_visible" in want:
+            res["n_visible"] = _new((n, n_az), sp, np.int32, like=pos)
+        _check(lib().turtle_stepper_viewshed_n(
+            self.h, C.c_long(n), _ptr(pos), n_az, _ptr(az), n_d, _ptr(ds), layer, C.c_double(target_height),
+            _ptr(res["visible"]), _ptr(res.get("sine")), _ptr(res.get("horizon")), _ptr(res.get("n_visible")), sp))
         return res
 
     def step(self, position, direction=None, resume=None, outputs=True):

@@ -25,6 +25,8 @@
  *   k_normal        batch normals of a layer's top surface (turtle_stepper_normal_n)
  *   k_horizon       the skyline around observers, one wave per line of sight: the highest of a
  *                   line's samples of a layer's top (turtle_stepper_horizon_n)
+ *   k_viewshed      which samples of those lines the observer sees: a wave-wide prefix maximum
+ *                   over chunks of 64 samples (turtle_stepper_viewshed_n)
  *   k_step          batch turtle_stepper_step [ref stepper.c:780-875]: the sample and
  *   k_step_fast     the tentative step; rays that crossed a boundary are listed
  *                   (k_step_fast: the fast-math body of the one-map / one-stack
@@ -460,6 +462,120 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
                                 if (range != nullptr) range[i] = best_range;
                         }
                 }
+        }
+}
+
+/* One sample of a line of turtle_stepper_viewshed_n, k_horizon's arithmetic: the sine of the
+ * elevation angle of the layer's top under p + s h as the observer p sees it (`ground`), and of the
+ * point `height` above it (`target`; the ground's own at height 0).  false where the definition
+ * skips the sample: no data there, or a point at the observer itself [ref ecef.c:194]. */
+template <int MODE, bool FAST>
+__device__ __forceinline__ bool d_viewshed_sample(const tamd_view & v, const OneCtx & ctx, int layer, double p0,
+    double p1, double p2, const double (&u)[3], const double (&h)[3], double s, double height, double & ground,
+    double & target)
+{
+        const double x = p0 + s * h[0], y = p1 + s * h[1], z = p2 + s * h[2];
+        double la, lo, al, top;
+        if (FAST) {
+                f_to_geodetic(x, y, z, la, lo, al);
+                /* The longitude is the closed form's in either arithmetic [ref ecef.c:86].  A line due
+                 * north or south of an observer on a whole degree runs ALONG a seam of the tiles, and
+                 * the last ulp of the longitude then says which tile answers: beside a missing tile,
+                 * whether a sample has data at all.  With the reference's expression the flags are the
+                 * reference's there too. */
+                if ((x != 0.) || (y != 0.)) lo = atan2(y, x) * 180. / kPi;
+        } else
+                d_to_geodetic(x, y, z, la, lo, al);
+        if (!d_layer_top<MODE>(v, ctx, layer, la, lo, top)) return false;
+        double g0, g1, g2;
+        d_from_geodetic(la, lo, top + 0., g0, g1, g2);
+        double d0 = g0 - p0, d1 = g1 - p1, d2 = g2 - p2;
+        double rr = d0 * d0 + d1 * d1 + d2 * d2;
+        if (rr <= FLT_EPSILON) return false;
+        ground = (u[0] * d0 + u[1] * d1 + u[2] * d2) / sqrt(rr);
+        if (height == 0.) {
+                target = ground;
+                return true;
+        }
+        d_from_geodetic(la, lo, top + height, g0, g1, g2);
+        d0 = g0 - p0, d1 = g1 - p1, d2 = g2 - p2;
+        rr = d0 * d0 + d1 * d1 + d2 * d2;
+        if (rr <= FLT_EPSILON) return false;
+        target = (u[0] * d0 + u[1] * d1 + u[2] * d2) / sqrt(rr);
+        return true;
+}
+
+/* turtle_stepper_viewshed_n: which samples of a line the observer sees.  One WAVE per item
+ * i = r * n_az + a as in k_horizon, four items a block, but a line is swept in CHUNKS of 64
+ * consecutive samples, k = base + lane: sample k is seen iff the target's sine is not below the
+ * maximum of the ground's sines of the samples before it, a prefix maximum.  Per chunk every lane
+ * evaluates its sample; an inclusive Hillis-Steele scan over the lanes (__shfl_up by 1 .. 32)
+ * gives the maximum up to each lane, the value one lane below (and `carry`, the maximum of the
+ * chunks before, wave-uniform) the horizon in front of it.  The chunk loop's bound is wave-uniform
+ * and nothing branches around the scan: a lane past the end, a skipped sample and a NaN contribute
+ * -HUGE_VAL.  A maximum rounds nothing, and of equal values (+0 and -0) the earlier one is kept
+ * as the sequential `>` keeps it: the outputs are the sequential loop's bits.  Lane l writes
+ * element base + l of each output; no LDS, no atomics, no scratch. */
+template <int MODE, bool FAST>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_viewshed(tamd_view v, int n_items, int n_az, int n_d,
+    const double * __restrict__ pos, const double * __restrict__ azimuth,
+    const double * __restrict__ distance, int layer, double height, signed char * __restrict__ visible,
+    double * __restrict__ sine, double * __restrict__ horizon, int * __restrict__ n_visible)
+{
+        OneCtx ctx;
+        d_load_ctx<MODE, false>(v, ctx);
+        const int lane = (int)(threadIdx.x & 63);
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        for (long i = blockIdx.x * 4L + wave; i < (long)n_items; i += (long)gridDim.x * 4L) {
+                const long r = i / n_az;
+                const int a = (int)(i - r * n_az);
+                const double p0 = pos[3 * r], p1 = pos[3 * r + 1], p2 = pos[3 * r + 2];
+                double lat0, lon0, alt0;
+                if (FAST)
+                        f_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
+                else
+                        d_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
+                double e[3], nn[3], u[3], h[3];
+                d_enu(lat0, lon0, e, nn, u);
+                { /* turtle_ecef_from_horizontal at elevation 0 [ref ecef.c:160-176] */
+                        const double az = azimuth[a] * kPi / 180.;
+                        const double el = 0. * kPi / 180.;
+                        const double ce = cos(el);
+                        const double q0 = ce * sin(az), q1 = ce * cos(az), q2 = sin(el);
+                        for (int j = 0; j < 3; j++) h[j] = q0 * e[j] + q1 * nn[j] + q2 * u[j];
+                }
+
+                const size_t first = (size_t)i * (size_t)n_d;
+                double carry = -HUGE_VAL;
+                int count = 0;
+                for (int base = 0; base < n_d; base += 64) { /* (wave-uniform: every lane reaches every shuffle) */
+                        const int k = base + lane;
+                        const bool in = k < n_d;
+                        double ground = -HUGE_VAL, target = -HUGE_VAL;
+                        bool data = false;
+                        if (in)
+                                data = d_viewshed_sample<MODE, FAST>(v, ctx, layer, p0, p1, p2, u, h, distance[k],
+                                    height, ground, target);
+                        /* (ground == ground: a NaN never raises the horizon) */
+                        double inclusive = (data && (ground == ground)) ? ground : -HUGE_VAL;
+                        for (int off = 1; off < 64; off <<= 1) {
+                                const double lower = __shfl_up(inclusive, off, 64);
+                                if (lane >= off) inclusive = (inclusive > lower) ? inclusive : lower;
+                        }
+                        double before = __shfl_up(inclusive, 1, 64);
+                        if (lane == 0) before = -HUGE_VAL;
+                        before = (before > carry) ? before : carry;
+                        const double last = __shfl(inclusive, 63, 64);
+                        carry = (last > carry) ? last : carry;
+                        const bool seen = data && (target >= before); /* (a NaN is never seen; grazing is) */
+                        count += __popcll(__ballot(seen));
+                        if (in) {
+                                visible[first + k] = data ? (signed char)seen : (signed char)-1;
+                                if (sine != nullptr) sine[first + k] = data ? target : __builtin_nan("");
+                                if (horizon != nullptr) horizon[first + k] = before;
+                        }
+                }
+                if ((n_visible != nullptr) && (lane == 0)) n_visible[i] = count;
         }
 }
 
@@ -2948,6 +3064,22 @@ extern "C" int tamd_k_horizon(struct tamd_view view, int n_items, int n_azimuths
                         return launch_blocks("k_horizon", k_horizon<decltype(mode)::value, decltype(fast)::value>,
                             grid_for(64L * n_items, 256), 0, view, n_items, n_azimuths, n_distances, pos, azimuth,
                             distance, layer, elevation, sample, range);
+                });
+        });
+}
+
+/* the same lines, every sample of each written: visible [n_items][n_distances] and the rest */
+extern "C" int tamd_k_viewshed(struct tamd_view view, int n_items, int n_azimuths, int n_distances,
+    const double * pos, const double * azimuth, const double * distance, int layer, double target_height,
+    signed char * visible, double * sine, double * horizon, int * n_visible)
+{
+        if (tamd_dev_init()) return 1;
+        if ((n_items <= 0) || (n_azimuths <= 0) || (n_distances <= 0)) return 0;
+        return with_mode(view.mode, [&](auto mode) {
+                return with_math(g_math_strict, [&](auto fast) {
+                        return launch_blocks("k_viewshed", k_viewshed<decltype(mode)::value, decltype(fast)::value>,
+                            grid_for(64L * n_items, 256), 0, view, n_items, n_azimuths, n_distances, pos, azimuth,
+                            distance, layer, target_height, visible, sine, horizon, n_visible);
                 });
         });
 }

@@ -118,6 +118,12 @@ int tamd_k_normal(struct tamd_view view, long n, const double * pos, const int *
 int tamd_k_horizon(struct tamd_view view, int n_items, int n_azimuths, int n_distances,
     const double * pos, const double * azimuth, const double * distance, int layer, double * elevation,
     int * sample, double * range);
+/* the viewshed (turtle_stepper_viewshed_n) over the same lines: every element of visible
+ * [n_items][n_distances] is written (1, 0, or -1 for a skipped sample), and of sine, horizon
+ * (same shape) and n_visible [n_items] where they are wanted (NULL: not) */
+int tamd_k_viewshed(struct tamd_view view, int n_items, int n_azimuths, int n_distances,
+    const double * pos, const double * azimuth, const double * distance, int layer, double target_height,
+    signed char * visible, double * sine, double * horizon, int * n_visible);
 int tamd_k_step(struct tamd_view view, long n, double * pos,
     const double * dir, double * lat, double * lon, double * alt,
     double * elev, double * step, int * index, int flags, struct tamd_paging pg);

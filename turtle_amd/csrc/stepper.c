@@ -784,6 +784,30 @@ enum turtle_return turtle_stepper_normal_n(struct turtle_stepper * stepper, long
         return TURTLE_RETURN_SUCCESS;
 }
 
+/* A wave cannot wait for a tile in the middle of its reduction or its scan: every tile of every
+ * stack in memory first (turtle_stack_load), as for a device view.  `caller`: the call's name,
+ * for the message. */
+static enum turtle_return stepper_load_all(struct turtle_stepper * stepper, struct tamd_error * error,
+    const char * caller)
+{
+        int i;
+        for (i = 0; i < stepper->n_data; i++) {
+                if (stepper->data[i].kind != TAMD_STACK) continue;
+                struct turtle_stack * stack = stepper->data[i].stack;
+                if (tamd_stack_budget(stack) < stack->n_files)
+                        return tamd_raise_(error, TURTLE_RETURN_DOMAIN_ERROR, __FILE__, __LINE__,
+                            "a stack of %d tiles cannot keep them all in memory (stack_size %d): "
+                            "%s reads resident tiles only", stack->n_files, stack->max_size, caller);
+                if (stack->n_loaded >= stack->n_files) continue;
+                if (tamd_geometry_view_held()) /* (loading takes what a view of this thread holds) */
+                        return tamd_raise_(error, TURTLE_RETURN_DOMAIN_ERROR, __FILE__, __LINE__,
+                            TAMD_VIEW_HELD_TEXT);
+                const enum turtle_return rc = turtle_stack_load(stack);
+                if (rc != TURTLE_RETURN_SUCCESS) return rc;
+        }
+        return TURTLE_RETURN_SUCCESS;
+}
+
 struct horizon_args {
         int n_items, n_azimuths, n_distances, layer;
         void *pos, *azimuth, *distance, *elevation, *sample, *range;
@@ -819,21 +843,8 @@ enum turtle_return turtle_stepper_horizon_n(struct turtle_stepper * stepper, lon
                 return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
                     "too many lines of sight (%ld observers x %d azimuths): the items of a call are numbered by ints",
                     n, n_azimuths);
-        /* a wave cannot wait for a tile in the middle of its reduction: every tile of every stack
-         * in memory first (turtle_stack_load), as for a device view */
-        int i;
-        for (i = 0; i < stepper->n_data; i++) {
-                if (stepper->data[i].kind != TAMD_STACK) continue;
-                struct turtle_stack * stack = stepper->data[i].stack;
-                if (tamd_stack_budget(stack) < stack->n_files)
-                        return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
-                            "a stack of %d tiles cannot keep them all in memory (stack_size %d): "
-                            "turtle_stepper_horizon_n reads resident tiles only", stack->n_files, stack->max_size);
-                if (stack->n_loaded >= stack->n_files) continue;
-                TAMD_VIEW_GUARD(); /* (loading takes what a view of this thread holds) */
-                const enum turtle_return rc = turtle_stack_load(stack);
-                if (rc != TURTLE_RETURN_SUCCESS) return rc;
-        }
+        const enum turtle_return loaded = stepper_load_all(stepper, &error_, "turtle_stepper_horizon_n");
+        if (loaded != TURTLE_RETURN_SUCCESS) return loaded;
         struct tamd_stage st = { 0 };
         struct horizon_args a = { (int)(n * n_azimuths), n_azimuths, n_distances, layer_index, NULL, NULL,
                 NULL, NULL, NULL, NULL, 0 };
@@ -846,6 +857,66 @@ enum turtle_return turtle_stepper_horizon_n(struct turtle_stepper * stepper, lon
         tamd_stage_add(&st, sample, items * sizeof(int), TAMD_OUT, &a.sample);
         if (tamd_stage_open(&st, space)) return TAMD_RAISE_DEVICE();
         const int rc = stepper_resident(stepper, &horizon_resident, &a);
+        stepper->last_rounds = 1;
+        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
+        if (a.paged)
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "a tile left its stack while the call was made: try again");
+        if (tamd_stage_close(&st)) return TAMD_RAISE_DEVICE();
+        return TURTLE_RETURN_SUCCESS;
+}
+
+struct viewshed_args {
+        int n_items, n_azimuths, n_distances, layer;
+        double target_height;
+        void *pos, *azimuth, *distance, *visible, *sine, *horizon, *n_visible;
+        int paged; /* out: a tile was not resident when the tables were made current */
+};
+
+static int viewshed_resident(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
+{
+        struct viewshed_args * a = p;
+        (void)pg, (void)round;
+        if (stepper_is_paged(stepper)) { /* (a tile another thread took meanwhile) */
+                a->paged = 1;
+                return 0;
+        }
+        return tamd_k_viewshed(stepper->view, a->n_items, a->n_azimuths, a->n_distances, a->pos, a->azimuth,
+            a->distance, a->layer, a->target_height, a->visible, a->sine, a->horizon, a->n_visible);
+}
+
+enum turtle_return turtle_stepper_viewshed_n(struct turtle_stepper * stepper, long n,
+    const double * position, int n_azimuths, const double * azimuth, int n_distances,
+    const double * distance, int layer_index, double target_height, signed char * visible, double * sine,
+    double * horizon, int * n_visible, int space)
+{
+        TAMD_ERROR_INIT(&turtle_stepper_viewshed_n);
+        if ((stepper == NULL) || (position == NULL) || (azimuth == NULL) || (distance == NULL) ||
+            (visible == NULL))
+                return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
+        if ((layer_index < 0) || (layer_index >= stepper->n_layers))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "no valid data");
+        if ((space != TURTLE_AMD_HOST) && (space != TURTLE_AMD_DEVICE))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid space (%d)", space);
+        if ((n <= 0) || (n_azimuths <= 0) || (n_distances <= 0)) return TURTLE_RETURN_SUCCESS;
+        if (n > (long)(INT_MAX / n_azimuths))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
+                    "too many lines of sight (%ld observers x %d azimuths): the items of a call are numbered by ints",
+                    n, n_azimuths);
+        const enum turtle_return loaded = stepper_load_all(stepper, &error_, "turtle_stepper_viewshed_n");
+        if (loaded != TURTLE_RETURN_SUCCESS) return loaded;
+        struct tamd_stage st = { 0 };
+        struct viewshed_args a = { (int)(n * n_azimuths), n_azimuths, n_distances, layer_index, target_height,
+                NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0 };
+        const size_t items = (size_t)a.n_items, elements = items * (size_t)n_distances;
+        tamd_stage_add(&st, position, 3 * (size_t)n * sizeof(double), TAMD_IN, &a.pos);
+        tamd_stage_add(&st, azimuth, (size_t)n_azimuths * sizeof(double), TAMD_IN, &a.azimuth);
+        tamd_stage_add(&st, distance, (size_t)n_distances * sizeof(double), TAMD_IN, &a.distance);
+        tamd_stage_add(&st, visible, elements * sizeof(signed char), TAMD_OUT, &a.visible); /* every */
+        tamd_stage_add(&st, sine, elements * sizeof(double), TAMD_OUT, &a.sine); /* element of each is */
+        tamd_stage_add(&st, horizon, elements * sizeof(double), TAMD_OUT, &a.horizon); /* written: nothing */
+        tamd_stage_add(&st, n_visible, items * sizeof(int), TAMD_OUT, &a.n_visible); /* to copy in */
+        if (tamd_stage_open(&st, space)) return TAMD_RAISE_DEVICE();
+        const int rc = stepper_resident(stepper, &viewshed_resident, &a);
         stepper->last_rounds = 1;
         if (rc != 0) return RAISE_ROUNDS(stepper, rc);
         if (a.paged)
