@@ -12,7 +12,6 @@ times those, to leave room for another libm build.  As a condition and not a mea
 bar may not exceed 1e-9: one ulp of latitude moves the ground by under 1e-9 m, so a larger
 difference is a bug.  Every best-to-second gap of the fixture is above 1e-8
 (tests/test_horizon_host.py), so the sample number is pinned on every line."""
-import os
 import subprocess
 
 import numpy as np
@@ -23,10 +22,10 @@ from turtle_amd import synth
 
 import horizon_cases as HC
 import normal_cases as NC
+import sight_cases as SC
+from sight_cases import flat, geometries, math_mode  # noqa: F401 (the fixtures, for pytest to find)
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # measured on the MI355X, the largest |sin(elevation) - expected| and |range - expected| (metres) of
 # each case, FAST / STRICT:  map 2.1e-16 / 3.5e-18 and 3.3e-11 / 3.6e-12;  stack 1.7e-13 / 1.4e-17 and
@@ -43,32 +42,6 @@ SENTINEL = HC.SENTINEL
 
 def test_the_bar_is_below_its_cap():
     assert max(BAR_SINE.values()) <= CAP_SINE
-
-
-@pytest.fixture(scope="module")
-def geometries(tmp_path_factory):
-    made = {}
-
-    def get(case):
-        if case not in made:
-            made[case] = NC.amd_geometry(case, str(tmp_path_factory.mktemp(case)))
-        return made[case]
-
-    yield get
-    for geo in made.values():
-        NC.destroy(geo)
-
-
-class math_mode:
-    def __init__(self, mode):
-        self.mode = mode
-
-    def __enter__(self):
-        TA.set_math(self.mode)
-
-    def __exit__(self, *exc):
-        TA.set_math("fast")
-        return False
 
 
 def run(st, position, azimuth, distance, layer, want=("range",)):
@@ -128,15 +101,6 @@ def test_against_the_reference(golden, geometries, case, math):
 
 
 # ---- 3: ties -----------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def flat():
-    st = TA.Stepper()
-    st.add_flat(0.0)
-    pos, _ = st.position(np.array([12.0]), np.array([34.0]), 800.0)
-    yield st, pos
-    st.destroy()
-
 
 def test_ties_go_to_the_smaller_k(flat):
     """over a flat layer seen from 800 m up the sine -h / s - s / 2R rises with the distance up to
@@ -274,53 +238,22 @@ def test_against_the_composition_of_the_older_calls(tmp_path):
     """a geometry larger than the fixture's: one rough tile of 1201 x 1201 nodes, 16 observers x 36
     azimuths x 200 distances, the whole profile from turtle_ecef_to_geodetic_n (STRICT),
     turtle_ecef_from_horizontal_n, turtle_stepper_position_n and numpy"""
-    synth.write_rough_hgt(str(tmp_path), 45, 3)
-    stack = TA.Stack(str(tmp_path), 0)
-    st = TA.Stepper()
-    st.add_stack(stack, 0.0)
-    rng = np.random.Generator(np.random.Philox(81))
-    n, n_az, n_d = 16, 36, 200
-    try:
+    with SC.rough_lines(str(tmp_path)) as r:
+        st, pos, az, dist = (r[k] for k in ("stepper", "position", "azimuth", "distance"))
         with math_mode("strict"):
-            pos, di = st.position(rng.uniform(45.2, 45.8, n), rng.uniform(3.2, 3.8, n), rng.uniform(2.0, 300.0, n))
-            assert (di == 0).all()
-            az = np.arange(n_az) * 10.0
-            dist = 100.0 * 600.0 ** (np.arange(n_d) / (n_d - 1.0))                  # 100 m to 60 km
             got = run(st, pos, az, dist, 0)
-            la0, lo0, _ = TA.ecef_to_geodetic(pos)
-            h = TA.ecef_from_horizontal(np.repeat(la0, n_az), np.repeat(lo0, n_az), np.tile(az, n),
-                                        np.zeros(n * n_az)).reshape(n, n_az, 1, 3)
-            p = pos.reshape(n, 1, 1, 3)
-            s = dist.reshape(1, 1, n_d)
-            q = np.stack([p[..., j] + s * h[..., j] for j in range(3)], -1)
-            la, lo, _ = TA.ecef_to_geodetic(q.reshape(-1, 3))
-            ground, di = st.position(la, lo, 0.0, 0)
-        lam, phi = lo0 * np.pi / 180.0, la0 * np.pi / 180.0
-        sl, cl, sp, cp = np.sin(lam), np.cos(lam), np.sin(phi), np.cos(phi)
-        up = np.stack([cl * cp, sl * cp, sp], -1).reshape(n, 1, 1, 3)
-        d = ground.reshape(n, n_az, n_d, 3) - p
-        rr = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            sine = (up[..., 0] * d[..., 0] + up[..., 1] * d[..., 1] + up[..., 2] * d[..., 2]) / np.sqrt(rr)
-        sine[(di.reshape(n, n_az, n_d) < 0) | (rr <= HC.FLT_EPSILON)] = np.nan
+        sine, _ = SC.composed_profile(st, pos, az, dist)
         assert np.isnan(sine).any() and not np.isnan(sine).all(-1).any()           # lines leave the tile
         want = np.nanargmax(sine, -1) + 1
         print("composition: winners on", len(set(want.ravel().tolist())), "different samples,",
               int((got["sample"] != want).sum()), "lines differ in the sample")
         check_against(sine, got, BAR_SINE["strict"], BAR_RANGE["strict"], "composition")
-    finally:
-        st.destroy()
-        stack.destroy()
 
 
 # ---- the example -------------------------------------------------------------------------------
 
 def test_horizon_example(tmp_path):
-    exe = str(tmp_path / "horizon")
-    subprocess.check_call(["gcc", "-O2", "-std=c99", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "horizon.c"), "-o", exe,
-                           "-L" + os.path.dirname(TA.library_path()), "-lturtle_amd",
-                           "-Wl,-rpath," + os.path.dirname(TA.library_path()), "-lm"])
+    exe = SC.build_example("horizon", tmp_path)
     tile = synth.write_rough_hgt(str(tmp_path), 45, 3)
     out = subprocess.run([exe, tile], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr

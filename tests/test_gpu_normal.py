@@ -19,6 +19,7 @@ import pytest
 import turtle_amd as TA
 
 import normal_cases as NC
+from sight_cases import geometries  # noqa: F401 (the fixture, for pytest to find)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,21 +31,6 @@ WORST = 2.17e-11
 BAR = 10 * WORST
 SENTINEL = -7.0
 ULP = 2.0 ** -52
-
-
-@pytest.fixture(scope="module")
-def geometries(tmp_path_factory):
-    made = {}
-
-    def get(case, stack_size=0):
-        key = (case, stack_size)
-        if key not in made:
-            made[key] = NC.amd_geometry(case, str(tmp_path_factory.mktemp(f"{case}_{stack_size}")), stack_size)
-        return made[key]
-
-    yield get
-    for geo in made.values():
-        NC.destroy(geo)
 
 
 def run(st, position, layer):

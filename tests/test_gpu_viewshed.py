@@ -22,8 +22,8 @@ measures its 20 winners a case), FAST / STRICT:
               layers_geoid 1.83e-12 / 1.83e-12: WORST_TARGET.
 |horizon - fixture| is at most 1.43e-11 / 1.09e-11 (lambert).  No flag differs in any case.
 
-The longitude of a sample is the closed form's atan2 in FAST as well (device.hip,
-d_viewshed_sample).  Observer 0 of layers_geoid stands at longitude 11 exactly and azimuth 0 runs
+The longitude of a sample is the closed form's atan2 in FAST as well (device.hip, d_sight_sample's
+CLOSED_LON).  Observer 0 of layers_geoid stands at longitude 11 exactly and azimuth 0 runs
 due north, along the seam between the stack's tile 10..11 degrees east and the MISSING tile north
 of latitude 1: the reference's transform returns 11 - 1 ulp there, the tile with data, and at 11.0
 its own turtle_stepper_position finds none.  With the fast transform's own atan2 five samples of
@@ -31,7 +31,6 @@ that line (116 to 119 and 123) came back -1 where the fixture has data; test_aga
 [layers_geoid-*-fast] is what holds the kernel to the reference's side of a seam.
 """
 import itertools
-import os
 import subprocess
 
 import numpy as np
@@ -42,11 +41,11 @@ from turtle_amd import synth
 
 import horizon_cases as HC
 import normal_cases as NC
+import sight_cases as SC
 import viewshed_cases as VC
+from sight_cases import flat, geometries, math_mode  # noqa: F401 (the fixtures, for pytest to find)
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CAP_SINE = 1e-9
 # tests/test_gpu_horizon.py: WORST_SINE, BAR_SINE (the ground's sines: the same expressions)
@@ -60,32 +59,6 @@ ALL = ("sine", "horizon", "n_visible")
 
 def test_the_bars_are_below_their_cap():
     assert max(BAR_GROUND.values()) <= CAP_SINE and max(BAR_TARGET.values()) <= CAP_SINE
-
-
-@pytest.fixture(scope="module")
-def geometries(tmp_path_factory):
-    made = {}
-
-    def get(case):
-        if case not in made:
-            made[case] = NC.amd_geometry(case, str(tmp_path_factory.mktemp(case)))
-        return made[case]
-
-    yield get
-    for geo in made.values():
-        NC.destroy(geo)
-
-
-class math_mode:
-    def __init__(self, mode):
-        self.mode = mode
-
-    def __enter__(self):
-        TA.set_math(self.mode)
-
-    def __exit__(self, *exc):
-        TA.set_math("fast")
-        return False
 
 
 def inputs(golden, case):
@@ -161,22 +134,10 @@ def test_the_scan_is_exact_on_the_fixture_cases(golden, geometries, case):
 def rough(tmp_path_factory):
     """one rough tile of 1201 x 1201 nodes, 16 observers x 36 azimuths x 200 distances: the inputs of
     test_gpu_horizon.py's composition test, and the call's answer over them (STRICT)"""
-    tmp = tmp_path_factory.mktemp("rough")
-    synth.write_rough_hgt(str(tmp), 45, 3)
-    stack = TA.Stack(str(tmp), 0)
-    st = TA.Stepper()
-    st.add_stack(stack, 0.0)
-    rng = np.random.Generator(np.random.Philox(81))
-    n, n_az, n_d = 16, 36, 200
-    with math_mode("strict"):
-        pos, di = st.position(rng.uniform(45.2, 45.8, n), rng.uniform(3.2, 3.8, n), rng.uniform(2.0, 300.0, n))
-        assert (di == 0).all()
-        az = np.arange(n_az) * 10.0
-        dist = 100.0 * 600.0 ** (np.arange(n_d) / (n_d - 1.0))                  # 100 m to 60 km
-        got = st.viewshed(pos, az, dist, 0)
-    yield dict(stepper=st, position=pos, azimuth=az, distance=dist, got=got)
-    st.destroy()
-    stack.destroy()
+    with SC.rough_lines(str(tmp_path_factory.mktemp("rough"))) as r:
+        with math_mode("strict"):
+            r["got"] = r["stepper"].viewshed(r["position"], r["azimuth"], r["distance"], 0)
+        yield r
 
 
 def test_the_scan_is_exact_on_a_rough_tile(rough):
@@ -211,15 +172,6 @@ def test_items_that_do_not_fill_a_block_and_one_item_alone(golden, geometries):
 
 
 # ---- 4: edges ------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def flat():
-    st = TA.Stepper()
-    st.add_flat(0.0)
-    pos, _ = st.position(np.array([12.0]), np.array([34.0]), 800.0)
-    yield st, pos
-    st.destroy()
-
 
 def test_repeated_distances_and_a_nan(flat):
     """over a flat layer seen from 800 m up the sine rises with the distance up to 101 km (see
@@ -289,25 +241,7 @@ def test_against_the_composition_of_the_older_calls(rough):
     these inputs: 109 825 samples with data, 19 158 of them visible, the smallest
     |sine - running maximum| 3.1e-7, none within 1e-9: nothing is expected to be left out.)"""
     st, pos, az, dist, got = (rough[k] for k in ("stepper", "position", "azimuth", "distance", "got"))
-    n, n_az, n_d = got["visible"].shape
-    with math_mode("strict"):
-        la0, lo0, _ = TA.ecef_to_geodetic(pos)
-        h = TA.ecef_from_horizontal(np.repeat(la0, n_az), np.repeat(lo0, n_az), np.tile(az, n),
-                                    np.zeros(n * n_az)).reshape(n, n_az, 1, 3)
-        p = pos.reshape(n, 1, 1, 3)
-        s = dist.reshape(1, 1, n_d)
-        q = np.stack([p[..., j] + s * h[..., j] for j in range(3)], -1)
-        la, lo, _ = TA.ecef_to_geodetic(q.reshape(-1, 3))
-        ground, di = st.position(la, lo, 0.0, 0)
-    lam, phi = lo0 * np.pi / 180.0, la0 * np.pi / 180.0
-    sl, cl, sp, cp = np.sin(lam), np.cos(lam), np.sin(phi), np.cos(phi)
-    up = np.stack([cl * cp, sl * cp, sp], -1).reshape(n, 1, 1, 3)
-    d = ground.reshape(n, n_az, n_d, 3) - p
-    rr = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
-    with np.errstate(invalid="ignore", divide="ignore"):
-        sine = (up[..., 0] * d[..., 0] + up[..., 1] * d[..., 1] + up[..., 2] * d[..., 2]) / np.sqrt(rr)
-    skipped = (di.reshape(n, n_az, n_d) < 0) | (rr <= HC.FLT_EPSILON)
-    sine[skipped] = np.nan
+    sine, skipped = SC.composed_profile(st, pos, az, dist)
     horizon = VC.running_maximum(sine)
     visible, _ = VC.follows(sine, horizon, skipped)
     bar = BAR_GROUND["strict"]
@@ -405,11 +339,7 @@ def test_a_stack_too_small_for_its_tiles_is_refused(golden, tmp_path):
 # ---- 8: the example --------------------------------------------------------------------------------
 
 def test_viewshed_example(tmp_path):
-    exe = str(tmp_path / "viewshed")
-    subprocess.check_call(["gcc", "-O2", "-std=c99", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "viewshed.c"), "-o", exe,
-                           "-L" + os.path.dirname(TA.library_path()), "-lturtle_amd",
-                           "-Wl,-rpath," + os.path.dirname(TA.library_path()), "-lm"])
+    exe = SC.build_example("viewshed", tmp_path)
     tile = synth.write_rough_hgt(str(tmp_path), 45, 3)
     out = subprocess.run([exe, tile], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr

@@ -136,6 +136,15 @@ def _new(shape, space, dtype=np.float64, like=None, zero=False):
     return (np.zeros if zero else np.empty)(shape, dtype=dtype)
 
 
+def _sight_lines(position, azimuth, distance):
+    """The inputs of the calls over lines of sight (horizon, viewshed), in one space:
+    -> sp, pos (n, 3), az (n_az,), ds (n_d,), n, n_az, n_d."""
+    sp = _space_of(position, azimuth, distance)
+    pos = _as(position, sp).reshape(-1, 3)
+    az, ds = _as(azimuth, sp).reshape(-1), _as(distance, sp).reshape(-1)
+    return sp, pos, az, ds, pos.shape[0], az.shape[0], ds.shape[0]
+
+
 def _ptr(a):
     if a is None:
         return None
@@ -654,10 +663,7 @@ class Stepper:
         1-based number of that sample and its range (metres).  Lines without a sample that has
         data get sample 0 and keep what `out` held (a prefilled elevation, or a dict of a prefilled
         "elevation" and / or "range"), zeros without one."""
-        sp = _space_of(position, azimuth, distance)
-        pos = _as(position, sp).reshape(-1, 3)
-        az, ds = _as(azimuth, sp).reshape(-1), _as(distance, sp).reshape(-1)
-        n, n_az, n_d = pos.shape[0], az.shape[0], ds.shape[0]
+        sp, pos, az, ds, n, n_az, n_d = _sight_lines(position, azimuth, distance)
         given = out if isinstance(out, dict) else dict(elevation=out)
         el, rng = given.get("elevation"), given.get("range")
         if el is None:
@@ -680,10 +686,7 @@ class Stepper:
         `layer` at each sample (1, 0, or -1 where the sample has no data or is the observer's own
         foot), the sine of the target's elevation angle (NaN where -1), the largest sine of the
         ground before the sample (-inf: none yet) and the number of samples seen on each line."""
-        sp = _space_of(position, azimuth, distance)
-        pos = _as(position, sp).reshape(-1, 3)
-        az, ds = _as(azimuth, sp).reshape(-1), _as(distance, sp).reshape(-1)
-        n, n_az, n_d = pos.shape[0], az.shape[0], ds.shape[0]
+        sp, pos, az, ds, n, n_az, n_d = _sight_lines(position, azimuth, distance)
         res = dict(visible=_new((n, n_az, n_d), sp, np.int8, like=pos))     # (the call writes every element
         for name in ("sine", "horizon"):                                    # of each: nothing to clear)
             if name in want:

@@ -390,6 +390,89 @@ __device__ __forceinline__ bool d_layer_top(const tamd_view & v, const OneCtx & 
         return false;
 }
 
+/* A line of sight of turtle_stepper_horizon_n and _viewshed_n: line a of observer r. */
+struct SightLine {
+        double p0, p1, p2; /* the observer */
+        double u[3];       /* its vertical */
+        double h[3];       /* the line's horizontal unit vector: the sample at distance s lies under p + s h */
+};
+
+/* The preamble of both kernels: the observer's geodetic coordinates, its frame, and h from the
+ * azimuth.  Wave-uniform, computed by every lane.  FAST: the to_geodetic transform only. */
+template <bool FAST>
+__device__ __forceinline__ void d_sight_line(const double * __restrict__ pos,
+    const double * __restrict__ azimuth, long r, int a, SightLine & line)
+{
+        const double p0 = pos[3 * r], p1 = pos[3 * r + 1], p2 = pos[3 * r + 2];
+        double lat0, lon0, alt0;
+        if (FAST)
+                f_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
+        else
+                d_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
+        double e[3], nn[3];
+        d_enu(lat0, lon0, e, nn, line.u);
+        { /* turtle_ecef_from_horizontal at elevation 0 [ref ecef.c:160-176] */
+                const double az = azimuth[a] * kPi / 180.;
+                const double el = 0. * kPi / 180.;
+                const double ce = cos(el);
+                const double q0 = ce * sin(az), q1 = ce * cos(az), q2 = sin(el);
+                for (int j = 0; j < 3; j++) line.h[j] = q0 * e[j] + q1 * nn[j] + q2 * line.u[j];
+        }
+        line.p0 = p0, line.p1 = p1, line.p2 = p2;
+}
+
+/* One sample of a line: the sine of the elevation angle of the layer's top under p + s h as the
+ * observer p sees it (`ground`, at `range`), and of the point `height` above it (`target`; the
+ * ground's own at height 0).  false where the definition skips the sample: no data there, or a
+ * point at the observer itself [ref ecef.c:194].  FAST: the to_geodetic transform only;
+ * everything else is the strict arithmetic.
+ *
+ * CLOSED_LON is the one deliberate difference between the two calls ("The seam"): in
+ * FAST arithmetic, true takes the sample's longitude from the closed form's atan2 [ref ecef.c:86],
+ * false keeps the fast transform's; STRICT has the closed form's either way.  k_viewshed passes
+ * true: a line due north or south of an observer on a whole degree runs ALONG a seam of the tiles,
+ * the last ulp of the longitude then says which tile answers -- beside a missing tile, whether a
+ * sample has data at all -- and the call reports every sample, so with the reference's expression
+ * its flags are the reference's there too.  k_horizon passes false: such a sample changes a
+ * skyline only if it was the winner, and its FAST outputs stay what they were.
+ *
+ * RANGE: `range` is returned (k_horizon); without it (k_viewshed) the parameter is left alone.  The
+ * operations are the same, sqrt then `/` (DESIGN 3.14 has what the switch is worth). */
+template <int MODE, bool FAST, bool CLOSED_LON, bool RANGE>
+__device__ __forceinline__ bool d_sight_sample(const tamd_view & v, const OneCtx & ctx, int layer,
+    const SightLine & line, double s, double height, double & ground, double & target, double & range)
+{
+        const double p0 = line.p0, p1 = line.p1, p2 = line.p2;
+        const double x = p0 + s * line.h[0], y = p1 + s * line.h[1], z = p2 + s * line.h[2];
+        double la, lo, al, top;
+        if (FAST) {
+                f_to_geodetic(x, y, z, la, lo, al);
+                if (CLOSED_LON && ((x != 0.) || (y != 0.))) lo = atan2(y, x) * 180. / kPi;
+        } else
+                d_to_geodetic(x, y, z, la, lo, al);
+        if (!d_layer_top<MODE>(v, ctx, layer, la, lo, top)) return false;
+        double g0, g1, g2;
+        d_from_geodetic(la, lo, top + 0., g0, g1, g2);
+        double d0 = g0 - p0, d1 = g1 - p1, d2 = g2 - p2;
+        double rr = d0 * d0 + d1 * d1 + d2 * d2;
+        if (rr <= FLT_EPSILON) return false;
+        if (RANGE) {
+                range = sqrt(rr);
+                ground = (line.u[0] * d0 + line.u[1] * d1 + line.u[2] * d2) / range;
+        } else
+                ground = (line.u[0] * d0 + line.u[1] * d1 + line.u[2] * d2) / sqrt(rr);
+        if (height == 0.) {
+                target = ground;
+                return true;
+        }
+        d_from_geodetic(la, lo, top + height, g0, g1, g2);
+        d0 = g0 - p0, d1 = g1 - p1, d2 = g2 - p2;
+        rr = d0 * d0 + d1 * d1 + d2 * d2;
+        if (rr <= FLT_EPSILON) return false;
+        target = (line.u[0] * d0 + line.u[1] * d1 + line.u[2] * d2) / sqrt(rr);
+        return true;
+}
+
 /* turtle_stepper_horizon_n: the skyline around observers.  One WAVE per item i = r * n_az + a
  * (line a of observer r), four items a block; lane l takes the samples k = l, l + 64, ... of the
  * line and keeps its own best (sine of the elevation angle, k + 1, range); the wave then reduces
@@ -411,40 +494,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
         for (long i = blockIdx.x * 4L + wave; i < (long)n_items; i += (long)gridDim.x * 4L) {
                 const long r = i / n_az;
                 const int a = (int)(i - r * n_az);
-                const double p0 = pos[3 * r], p1 = pos[3 * r + 1], p2 = pos[3 * r + 2];
-                double lat0, lon0, alt0;
-                if (FAST)
-                        f_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
-                else
-                        d_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
-                double e[3], nn[3], u[3], h[3];
-                d_enu(lat0, lon0, e, nn, u);
-                { /* turtle_ecef_from_horizontal at elevation 0 [ref ecef.c:160-176] */
-                        const double az = azimuth[a] * kPi / 180.;
-                        const double el = 0. * kPi / 180.;
-                        const double ce = cos(el);
-                        const double q0 = ce * sin(az), q1 = ce * cos(az), q2 = sin(el);
-                        for (int j = 0; j < 3; j++) h[j] = q0 * e[j] + q1 * nn[j] + q2 * u[j];
-                }
+                SightLine line;
+                d_sight_line<FAST>(pos, azimuth, r, a, line);
 
                 double best = -HUGE_VAL, best_range = 0.;
                 int best_k = 0;
                 for (int k = lane; k < n_d; k += 64) {
-                        const double s = distance[k];
-                        const double x = p0 + s * h[0], y = p1 + s * h[1], z = p2 + s * h[2];
-                        double la, lo, al, top;
-                        if (FAST)
-                                f_to_geodetic(x, y, z, la, lo, al);
-                        else
-                                d_to_geodetic(x, y, z, la, lo, al);
-                        if (!d_layer_top<MODE>(v, ctx, layer, la, lo, top)) continue;
-                        double g0, g1, g2;
-                        d_from_geodetic(la, lo, top + 0., g0, g1, g2);
-                        const double d0 = g0 - p0, d1 = g1 - p1, d2 = g2 - p2;
-                        double rr = d0 * d0 + d1 * d1 + d2 * d2;
-                        if (rr <= FLT_EPSILON) continue; /* [ref ecef.c:194] */
-                        rr = sqrt(rr);
-                        const double arg = (u[0] * d0 + u[1] * d1 + u[2] * d2) / rr;
+                        /* (set: left undefined where the sample is skipped, they cost 12 to 24 B of scratch) */
+                        double arg = 0., same = 0., rr = 0.;
+                        if (!d_sight_sample<MODE, FAST, false, true>(v, ctx, layer, line, distance[k], 0., arg, same, rr))
+                                continue;
                         if (arg > best) best = arg, best_k = k + 1, best_range = rr; /* (a NaN never wins) */
                 }
                 for (int off = 32; off > 0; off >>= 1) {
@@ -463,46 +522,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
                         }
                 }
         }
-}
-
-/* One sample of a line of turtle_stepper_viewshed_n, k_horizon's arithmetic: the sine of the
- * elevation angle of the layer's top under p + s h as the observer p sees it (`ground`), and of the
- * point `height` above it (`target`; the ground's own at height 0).  false where the definition
- * skips the sample: no data there, or a point at the observer itself [ref ecef.c:194]. */
-template <int MODE, bool FAST>
-__device__ __forceinline__ bool d_viewshed_sample(const tamd_view & v, const OneCtx & ctx, int layer, double p0,
-    double p1, double p2, const double (&u)[3], const double (&h)[3], double s, double height, double & ground,
-    double & target)
-{
-        const double x = p0 + s * h[0], y = p1 + s * h[1], z = p2 + s * h[2];
-        double la, lo, al, top;
-        if (FAST) {
-                f_to_geodetic(x, y, z, la, lo, al);
-                /* The longitude is the closed form's in either arithmetic [ref ecef.c:86].  A line due
-                 * north or south of an observer on a whole degree runs ALONG a seam of the tiles, and
-                 * the last ulp of the longitude then says which tile answers: beside a missing tile,
-                 * whether a sample has data at all.  With the reference's expression the flags are the
-                 * reference's there too. */
-                if ((x != 0.) || (y != 0.)) lo = atan2(y, x) * 180. / kPi;
-        } else
-                d_to_geodetic(x, y, z, la, lo, al);
-        if (!d_layer_top<MODE>(v, ctx, layer, la, lo, top)) return false;
-        double g0, g1, g2;
-        d_from_geodetic(la, lo, top + 0., g0, g1, g2);
-        double d0 = g0 - p0, d1 = g1 - p1, d2 = g2 - p2;
-        double rr = d0 * d0 + d1 * d1 + d2 * d2;
-        if (rr <= FLT_EPSILON) return false;
-        ground = (u[0] * d0 + u[1] * d1 + u[2] * d2) / sqrt(rr);
-        if (height == 0.) {
-                target = ground;
-                return true;
-        }
-        d_from_geodetic(la, lo, top + height, g0, g1, g2);
-        d0 = g0 - p0, d1 = g1 - p1, d2 = g2 - p2;
-        rr = d0 * d0 + d1 * d1 + d2 * d2;
-        if (rr <= FLT_EPSILON) return false;
-        target = (u[0] * d0 + u[1] * d1 + u[2] * d2) / sqrt(rr);
-        return true;
 }
 
 /* turtle_stepper_viewshed_n: which samples of a line the observer sees.  One WAVE per item
@@ -529,21 +548,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
         for (long i = blockIdx.x * 4L + wave; i < (long)n_items; i += (long)gridDim.x * 4L) {
                 const long r = i / n_az;
                 const int a = (int)(i - r * n_az);
-                const double p0 = pos[3 * r], p1 = pos[3 * r + 1], p2 = pos[3 * r + 2];
-                double lat0, lon0, alt0;
-                if (FAST)
-                        f_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
-                else
-                        d_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
-                double e[3], nn[3], u[3], h[3];
-                d_enu(lat0, lon0, e, nn, u);
-                { /* turtle_ecef_from_horizontal at elevation 0 [ref ecef.c:160-176] */
-                        const double az = azimuth[a] * kPi / 180.;
-                        const double el = 0. * kPi / 180.;
-                        const double ce = cos(el);
-                        const double q0 = ce * sin(az), q1 = ce * cos(az), q2 = sin(el);
-                        for (int j = 0; j < 3; j++) h[j] = q0 * e[j] + q1 * nn[j] + q2 * u[j];
-                }
+                SightLine line;
+                d_sight_line<FAST>(pos, azimuth, r, a, line);
 
                 const size_t first = (size_t)i * (size_t)n_d;
                 double carry = -HUGE_VAL;
@@ -553,9 +559,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
                         const bool in = k < n_d;
                         double ground = -HUGE_VAL, target = -HUGE_VAL;
                         bool data = false;
-                        if (in)
-                                data = d_viewshed_sample<MODE, FAST>(v, ctx, layer, p0, p1, p2, u, h, distance[k],
-                                    height, ground, target);
+                        if (in) {
+                                double rr; /* (RANGE false: not written) */
+                                data = d_sight_sample<MODE, FAST, true, false>(v, ctx, layer, line, distance[k], height,
+                                    ground, target, rr);
+                        }
                         /* (ground == ground: a NaN never raises the horizon) */
                         double inclusive = (data && (ground == ground)) ? ground : -HUGE_VAL;
                         for (int off = 1; off < 64; off <<= 1) {
@@ -3052,19 +3060,26 @@ extern "C" int tamd_k_normal(struct tamd_view view, long n, const double * pos, 
         });
 }
 
-/* n_items = observers x azimuths lines, one wave each, four to a block */
-extern "C" int tamd_k_horizon(struct tamd_view view, int n_items, int n_azimuths, int n_distances,
-    const double * pos, const double * azimuth, const double * distance, int layer, double * elevation,
-    int * sample, double * range)
+/* A kernel over n_items = observers x azimuths lines of sight, one wave each, four to a block:
+ * `launch(mode, fast, grid)` names the instance and passes its arguments. */
+template <class Launch>
+static int launch_sight(struct tamd_view view, int n_items, int n_azimuths, int n_distances, Launch launch)
 {
         if (tamd_dev_init()) return 1;
         if ((n_items <= 0) || (n_azimuths <= 0) || (n_distances <= 0)) return 0;
         return with_mode(view.mode, [&](auto mode) {
-                return with_math(g_math_strict, [&](auto fast) {
-                        return launch_blocks("k_horizon", k_horizon<decltype(mode)::value, decltype(fast)::value>,
-                            grid_for(64L * n_items, 256), 0, view, n_items, n_azimuths, n_distances, pos, azimuth,
-                            distance, layer, elevation, sample, range);
-                });
+                return with_math(g_math_strict,
+                    [&](auto fast) { return launch(mode, fast, grid_for(64L * n_items, 256)); });
+        });
+}
+
+extern "C" int tamd_k_horizon(struct tamd_view view, int n_items, int n_azimuths, int n_distances,
+    const double * pos, const double * azimuth, const double * distance, int layer, double * elevation,
+    int * sample, double * range)
+{
+        return launch_sight(view, n_items, n_azimuths, n_distances, [&](auto mode, auto fast, auto grid) {
+                return launch_blocks("k_horizon", k_horizon<decltype(mode)::value, decltype(fast)::value>, grid, 0,
+                    view, n_items, n_azimuths, n_distances, pos, azimuth, distance, layer, elevation, sample, range);
         });
 }
 
@@ -3073,14 +3088,10 @@ extern "C" int tamd_k_viewshed(struct tamd_view view, int n_items, int n_azimuth
     const double * pos, const double * azimuth, const double * distance, int layer, double target_height,
     signed char * visible, double * sine, double * horizon, int * n_visible)
 {
-        if (tamd_dev_init()) return 1;
-        if ((n_items <= 0) || (n_azimuths <= 0) || (n_distances <= 0)) return 0;
-        return with_mode(view.mode, [&](auto mode) {
-                return with_math(g_math_strict, [&](auto fast) {
-                        return launch_blocks("k_viewshed", k_viewshed<decltype(mode)::value, decltype(fast)::value>,
-                            grid_for(64L * n_items, 256), 0, view, n_items, n_azimuths, n_distances, pos, azimuth,
-                            distance, layer, target_height, visible, sine, horizon, n_visible);
-                });
+        return launch_sight(view, n_items, n_azimuths, n_distances, [&](auto mode, auto fast, auto grid) {
+                return launch_blocks("k_viewshed", k_viewshed<decltype(mode)::value, decltype(fast)::value>, grid, 0,
+                    view, n_items, n_azimuths, n_distances, pos, azimuth, distance, layer, target_height, visible,
+                    sine, horizon, n_visible);
         });
 }
 

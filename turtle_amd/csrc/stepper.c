@@ -643,6 +643,31 @@ static int stepper_resident(struct turtle_stepper * stepper, stepper_round_t * l
         return rc;
 }
 
+/* Every tile of every stack in memory (turtle_stack_load): what a device view needs before its
+ * span begins, and the calls over lines of sight before they launch (a wave cannot wait for a tile
+ * in the middle of its reduction or its scan).  `who` `does`: the message's clause, "<who> <does>
+ * resident tiles only". */
+static enum turtle_return stepper_load_all(struct turtle_stepper * stepper, struct tamd_error * error,
+    const char * who, const char * does)
+{
+        int i;
+        for (i = 0; i < stepper->n_data; i++) {
+                if (stepper->data[i].kind != TAMD_STACK) continue;
+                struct turtle_stack * stack = stepper->data[i].stack;
+                if (tamd_stack_budget(stack) < stack->n_files)
+                        return tamd_raise_(error, TURTLE_RETURN_DOMAIN_ERROR, __FILE__, __LINE__,
+                            "a stack of %d tiles cannot keep them all in memory (stack_size %d): "
+                            "%s %s resident tiles only", stack->n_files, stack->max_size, who, does);
+                if (stack->n_loaded >= stack->n_files) continue;
+                if (tamd_geometry_view_held()) /* (loading takes what a view of this thread holds) */
+                        return tamd_raise_(error, TURTLE_RETURN_DOMAIN_ERROR, __FILE__, __LINE__,
+                            TAMD_VIEW_HELD_TEXT);
+                const enum turtle_return rc = turtle_stack_load(stack);
+                if (rc != TURTLE_RETURN_SUCCESS) return rc;
+        }
+        return TURTLE_RETURN_SUCCESS;
+}
+
 /* ---- a device view: the geometry lent to the caller's own kernel ------------- */
 
 void turtle_amd_view_layout(int * version, size_t * size)
@@ -662,20 +687,8 @@ enum turtle_return turtle_amd_stepper_view_acquire(struct turtle_stepper * stepp
                     "library's turtle_amd_device.h", size, sizeof(struct turtle_amd_view), TURTLE_AMD_VIEW_VERSION);
         if (stepper->view_out) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "the stepper's view is out already");
         if (tamd_dev_init()) return TAMD_RAISE_DEVICE();
-        /* every tile of every stack in memory (turtle_stack_load), before the span begins */
-        int i;
-        for (i = 0; i < stepper->n_data; i++) {
-                if (stepper->data[i].kind != TAMD_STACK) continue;
-                struct turtle_stack * st = stepper->data[i].stack;
-                if (tamd_stack_budget(st) < st->n_files)
-                        return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
-                            "a stack of %d tiles cannot keep them all in memory (stack_size %d): a device view "
-                            "names resident tiles only", st->n_files, st->max_size);
-                if (st->n_loaded >= st->n_files) continue;
-                TAMD_VIEW_GUARD(); /* (loading takes what another view of this thread holds) */
-                const enum turtle_return rc = turtle_stack_load(st);
-                if (rc != TURTLE_RETURN_SUCCESS) return rc;
-        }
+        const enum turtle_return loaded = stepper_load_all(stepper, &error_, "a device view", "names");
+        if (loaded != TURTLE_RETURN_SUCCESS) return loaded;
         tamd_geometry_use_begin();
         int rc = FLATTEN(stepper);
         int paged = 0;
@@ -784,46 +797,72 @@ enum turtle_return turtle_stepper_normal_n(struct turtle_stepper * stepper, long
         return TURTLE_RETURN_SUCCESS;
 }
 
-/* A wave cannot wait for a tile in the middle of its reduction or its scan: every tile of every
- * stack in memory first (turtle_stack_load), as for a device view.  `caller`: the call's name,
- * for the message. */
-static enum turtle_return stepper_load_all(struct turtle_stepper * stepper, struct tamd_error * error,
-    const char * caller)
+/* What the calls over lines of sight (observers x azimuths x distances, one wave a line) share:
+ * the lines, staged.  Each call's own arguments embed it first. */
+struct sight_lines {
+        struct tamd_stage stage;
+        int n_items, n_azimuths, n_distances, layer; /* n_items 0: nothing to do */
+        void *pos, *azimuth, *distance;
+        int paged; /* out: a tile was not resident when the tables were made current */
+};
+
+#define error_ (*error) /* (the TAMD_RAISE macros name it: the messages carry the caller's name) */
+
+/* After the caller's NULL checks: the other checks in their order, every tile in memory, the three
+ * inputs staged.  The caller adds its outputs to l->stage, then sight_run. */
+static enum turtle_return sight_begin(struct tamd_error * error, struct sight_lines * l,
+    struct turtle_stepper * stepper, long n, const double * position, int n_azimuths, const double * azimuth,
+    int n_distances, const double * distance, int layer_index, int space)
 {
-        int i;
-        for (i = 0; i < stepper->n_data; i++) {
-                if (stepper->data[i].kind != TAMD_STACK) continue;
-                struct turtle_stack * stack = stepper->data[i].stack;
-                if (tamd_stack_budget(stack) < stack->n_files)
-                        return tamd_raise_(error, TURTLE_RETURN_DOMAIN_ERROR, __FILE__, __LINE__,
-                            "a stack of %d tiles cannot keep them all in memory (stack_size %d): "
-                            "%s reads resident tiles only", stack->n_files, stack->max_size, caller);
-                if (stack->n_loaded >= stack->n_files) continue;
-                if (tamd_geometry_view_held()) /* (loading takes what a view of this thread holds) */
-                        return tamd_raise_(error, TURTLE_RETURN_DOMAIN_ERROR, __FILE__, __LINE__,
-                            TAMD_VIEW_HELD_TEXT);
-                const enum turtle_return rc = turtle_stack_load(stack);
-                if (rc != TURTLE_RETURN_SUCCESS) return rc;
-        }
+        if ((layer_index < 0) || (layer_index >= stepper->n_layers))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "no valid data");
+        if ((space != TURTLE_AMD_HOST) && (space != TURTLE_AMD_DEVICE))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid space (%d)", space);
+        if ((n <= 0) || (n_azimuths <= 0) || (n_distances <= 0)) return TURTLE_RETURN_SUCCESS;
+        if (n > (long)(INT_MAX / n_azimuths))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
+                    "too many lines of sight (%ld observers x %d azimuths): the items of a call are numbered by ints",
+                    n, n_azimuths);
+        const enum turtle_return loaded =
+            stepper_load_all(stepper, error, turtle_error_function(error->function), "reads");
+        if (loaded != TURTLE_RETURN_SUCCESS) return loaded;
+        l->n_items = (int)(n * n_azimuths), l->n_azimuths = n_azimuths, l->n_distances = n_distances;
+        l->layer = layer_index;
+        tamd_stage_add(&l->stage, position, 3 * (size_t)n * sizeof(double), TAMD_IN, &l->pos);
+        tamd_stage_add(&l->stage, azimuth, (size_t)n_azimuths * sizeof(double), TAMD_IN, &l->azimuth);
+        tamd_stage_add(&l->stage, distance, (size_t)n_distances * sizeof(double), TAMD_IN, &l->distance);
         return TURTLE_RETURN_SUCCESS;
 }
 
+/* `launch`, the call's own kernel over `args` (which embed l), and the closing sequence */
+static enum turtle_return sight_run(struct tamd_error * error, struct sight_lines * l,
+    struct turtle_stepper * stepper, int space, stepper_round_t * launch, void * args)
+{
+        if (tamd_stage_open(&l->stage, space)) return TAMD_RAISE_DEVICE();
+        const int rc = stepper_resident(stepper, launch, args);
+        stepper->last_rounds = 1;
+        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
+        if (l->paged)
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "a tile left its stack while the call was made: try again");
+        if (tamd_stage_close(&l->stage)) return TAMD_RAISE_DEVICE();
+        return TURTLE_RETURN_SUCCESS;
+}
+
+#undef error_
+
 struct horizon_args {
-        int n_items, n_azimuths, n_distances, layer;
-        void *pos, *azimuth, *distance, *elevation, *sample, *range;
-        int paged; /* out: a tile was not resident when the tables were made current */
+        struct sight_lines lines;
+        void *elevation, *sample, *range;
 };
 
 static int horizon_resident(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
 {
         struct horizon_args * a = p;
+        struct sight_lines * l = &a->lines;
         (void)pg, (void)round;
-        if (stepper_is_paged(stepper)) { /* (a tile another thread took meanwhile) */
-                a->paged = 1;
-                return 0;
-        }
-        return tamd_k_horizon(stepper->view, a->n_items, a->n_azimuths, a->n_distances, a->pos, a->azimuth,
-            a->distance, a->layer, a->elevation, a->sample, a->range);
+        if ((l->paged = stepper_is_paged(stepper))) return 0; /* (a tile another thread took meanwhile) */
+        return tamd_k_horizon(stepper->view, l->n_items, l->n_azimuths, l->n_distances, l->pos, l->azimuth,
+            l->distance, l->layer, a->elevation, a->sample, a->range);
 }
 
 enum turtle_return turtle_stepper_horizon_n(struct turtle_stepper * stepper, long n,
@@ -834,54 +873,31 @@ enum turtle_return turtle_stepper_horizon_n(struct turtle_stepper * stepper, lon
         if ((stepper == NULL) || (position == NULL) || (azimuth == NULL) || (distance == NULL) ||
             (elevation == NULL) || (sample == NULL))
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
-        if ((layer_index < 0) || (layer_index >= stepper->n_layers))
-                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "no valid data");
-        if ((space != TURTLE_AMD_HOST) && (space != TURTLE_AMD_DEVICE))
-                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid space (%d)", space);
-        if ((n <= 0) || (n_azimuths <= 0) || (n_distances <= 0)) return TURTLE_RETURN_SUCCESS;
-        if (n > (long)(INT_MAX / n_azimuths))
-                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
-                    "too many lines of sight (%ld observers x %d azimuths): the items of a call are numbered by ints",
-                    n, n_azimuths);
-        const enum turtle_return loaded = stepper_load_all(stepper, &error_, "turtle_stepper_horizon_n");
-        if (loaded != TURTLE_RETURN_SUCCESS) return loaded;
-        struct tamd_stage st = { 0 };
-        struct horizon_args a = { (int)(n * n_azimuths), n_azimuths, n_distances, layer_index, NULL, NULL,
-                NULL, NULL, NULL, NULL, 0 };
-        const size_t items = (size_t)a.n_items;
-        tamd_stage_add(&st, position, 3 * (size_t)n * sizeof(double), TAMD_IN, &a.pos);
-        tamd_stage_add(&st, azimuth, (size_t)n_azimuths * sizeof(double), TAMD_IN, &a.azimuth);
-        tamd_stage_add(&st, distance, (size_t)n_distances * sizeof(double), TAMD_IN, &a.distance);
-        tamd_stage_add(&st, elevation, items * sizeof(double), TAMD_INOUT, &a.elevation); /* lines without */
-        tamd_stage_add(&st, range, items * sizeof(double), TAMD_INOUT, &a.range); /* a sample keep theirs */
-        tamd_stage_add(&st, sample, items * sizeof(int), TAMD_OUT, &a.sample);
-        if (tamd_stage_open(&st, space)) return TAMD_RAISE_DEVICE();
-        const int rc = stepper_resident(stepper, &horizon_resident, &a);
-        stepper->last_rounds = 1;
-        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
-        if (a.paged)
-                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "a tile left its stack while the call was made: try again");
-        if (tamd_stage_close(&st)) return TAMD_RAISE_DEVICE();
-        return TURTLE_RETURN_SUCCESS;
+        struct horizon_args a = { 0 };
+        const enum turtle_return rc = sight_begin(&error_, &a.lines, stepper, n, position, n_azimuths, azimuth,
+            n_distances, distance, layer_index, space);
+        if ((rc != TURTLE_RETURN_SUCCESS) || (a.lines.n_items == 0)) return rc;
+        const size_t items = (size_t)a.lines.n_items;
+        tamd_stage_add(&a.lines.stage, elevation, items * sizeof(double), TAMD_INOUT, &a.elevation); /* lines without */
+        tamd_stage_add(&a.lines.stage, range, items * sizeof(double), TAMD_INOUT, &a.range); /* a sample keep theirs */
+        tamd_stage_add(&a.lines.stage, sample, items * sizeof(int), TAMD_OUT, &a.sample);
+        return sight_run(&error_, &a.lines, stepper, space, &horizon_resident, &a);
 }
 
 struct viewshed_args {
-        int n_items, n_azimuths, n_distances, layer;
+        struct sight_lines lines;
         double target_height;
-        void *pos, *azimuth, *distance, *visible, *sine, *horizon, *n_visible;
-        int paged; /* out: a tile was not resident when the tables were made current */
+        void *visible, *sine, *horizon, *n_visible;
 };
 
 static int viewshed_resident(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
 {
         struct viewshed_args * a = p;
+        struct sight_lines * l = &a->lines;
         (void)pg, (void)round;
-        if (stepper_is_paged(stepper)) { /* (a tile another thread took meanwhile) */
-                a->paged = 1;
-                return 0;
-        }
-        return tamd_k_viewshed(stepper->view, a->n_items, a->n_azimuths, a->n_distances, a->pos, a->azimuth,
-            a->distance, a->layer, a->target_height, a->visible, a->sine, a->horizon, a->n_visible);
+        if ((l->paged = stepper_is_paged(stepper))) return 0; /* (a tile another thread took meanwhile) */
+        return tamd_k_viewshed(stepper->view, l->n_items, l->n_azimuths, l->n_distances, l->pos, l->azimuth,
+            l->distance, l->layer, a->target_height, a->visible, a->sine, a->horizon, a->n_visible);
 }
 
 enum turtle_return turtle_stepper_viewshed_n(struct turtle_stepper * stepper, long n,
@@ -893,36 +909,17 @@ enum turtle_return turtle_stepper_viewshed_n(struct turtle_stepper * stepper, lo
         if ((stepper == NULL) || (position == NULL) || (azimuth == NULL) || (distance == NULL) ||
             (visible == NULL))
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
-        if ((layer_index < 0) || (layer_index >= stepper->n_layers))
-                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "no valid data");
-        if ((space != TURTLE_AMD_HOST) && (space != TURTLE_AMD_DEVICE))
-                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid space (%d)", space);
-        if ((n <= 0) || (n_azimuths <= 0) || (n_distances <= 0)) return TURTLE_RETURN_SUCCESS;
-        if (n > (long)(INT_MAX / n_azimuths))
-                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
-                    "too many lines of sight (%ld observers x %d azimuths): the items of a call are numbered by ints",
-                    n, n_azimuths);
-        const enum turtle_return loaded = stepper_load_all(stepper, &error_, "turtle_stepper_viewshed_n");
-        if (loaded != TURTLE_RETURN_SUCCESS) return loaded;
-        struct tamd_stage st = { 0 };
-        struct viewshed_args a = { (int)(n * n_azimuths), n_azimuths, n_distances, layer_index, target_height,
-                NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0 };
-        const size_t items = (size_t)a.n_items, elements = items * (size_t)n_distances;
-        tamd_stage_add(&st, position, 3 * (size_t)n * sizeof(double), TAMD_IN, &a.pos);
-        tamd_stage_add(&st, azimuth, (size_t)n_azimuths * sizeof(double), TAMD_IN, &a.azimuth);
-        tamd_stage_add(&st, distance, (size_t)n_distances * sizeof(double), TAMD_IN, &a.distance);
-        tamd_stage_add(&st, visible, elements * sizeof(signed char), TAMD_OUT, &a.visible); /* every */
-        tamd_stage_add(&st, sine, elements * sizeof(double), TAMD_OUT, &a.sine); /* element of each is */
-        tamd_stage_add(&st, horizon, elements * sizeof(double), TAMD_OUT, &a.horizon); /* written: nothing */
-        tamd_stage_add(&st, n_visible, items * sizeof(int), TAMD_OUT, &a.n_visible); /* to copy in */
-        if (tamd_stage_open(&st, space)) return TAMD_RAISE_DEVICE();
-        const int rc = stepper_resident(stepper, &viewshed_resident, &a);
-        stepper->last_rounds = 1;
-        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
-        if (a.paged)
-                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "a tile left its stack while the call was made: try again");
-        if (tamd_stage_close(&st)) return TAMD_RAISE_DEVICE();
-        return TURTLE_RETURN_SUCCESS;
+        struct viewshed_args a = { 0 };
+        const enum turtle_return rc = sight_begin(&error_, &a.lines, stepper, n, position, n_azimuths, azimuth,
+            n_distances, distance, layer_index, space);
+        if ((rc != TURTLE_RETURN_SUCCESS) || (a.lines.n_items == 0)) return rc;
+        const size_t items = (size_t)a.lines.n_items, elements = items * (size_t)n_distances;
+        a.target_height = target_height;
+        tamd_stage_add(&a.lines.stage, visible, elements * sizeof(signed char), TAMD_OUT, &a.visible); /* every */
+        tamd_stage_add(&a.lines.stage, sine, elements * sizeof(double), TAMD_OUT, &a.sine); /* element of each is */
+        tamd_stage_add(&a.lines.stage, horizon, elements * sizeof(double), TAMD_OUT, &a.horizon); /* written: nothing */
+        tamd_stage_add(&a.lines.stage, n_visible, items * sizeof(int), TAMD_OUT, &a.n_visible); /* to copy in */
+        return sight_run(&error_, &a.lines, stepper, space, &viewshed_resident, &a);
 }
 
 /* Grow-only scratch of the batch calls: 4 n ints (the rays a trace hands from
