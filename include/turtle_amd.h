@@ -658,6 +658,64 @@ TURTLE_API enum turtle_return turtle_stepper_viewshed_n(
     double * sine /* same shape, or NULL */, double * horizon /* same shape, or NULL */,
     int * n_visible /* [n][n_azimuths], or NULL */, int space);
 
+/* Flags of turtle_stepper_clearance_n. */
+enum turtle_amd_clearance_flags {
+        /* line r joins observer[r] to target[r] (m must equal n); outputs are [n] */
+        TURTLE_AMD_CLEARANCE_PAIRED = 1
+};
+
+/* The clearance of point-to-point lines: which of n observers and m targets (antennas, shower
+ * maxima in the air, telescope sites, the nodes of a map lifted by turtle_stepper_position_n) see
+ * each other over the top of a layer, and by what margin.  Where the two calls above follow an
+ * observer's horizontal tangent and judge by angles, this one samples the true straight chord
+ * between the two points, at the fractions `fraction` of it (shared by all lines, in the same
+ * memory space as the other arrays), and reduces it to its minimum height above the layer's top.
+ * Item i = r * m + t is the line from observer r to target t, the outputs observer-major [n][m];
+ * with TURTLE_AMD_CLEARANCE_PAIRED item i = r is the line from observer r to target r and the
+ * outputs are [n].  For every item, exactly this, with the reference's functions:
+ *
+ *     p = observer[r];  t = target[..];  d[j] = t[j] - p[j];
+ *     best = HUGE_VAL;  best_k = 0;  count = 0;
+ *     for (k = 0; k < n_fractions; k++) {
+ *             f = fraction[k];  q[j] = p[j] + f * d[j];                     (a product, then a sum)
+ *             turtle_ecef_to_geodetic(q, &la, &lo, &al);                    (al is not used)
+ *             turtle_stepper_position(stepper, la, lo, 0., layer_index, g, &di);
+ *             if (di < 0) continue;                                         (no data under the sample)
+ *             count++;
+ *             U = (cos(lo) cos(la), sin(lo) cos(la), sin(la));    [ref ecef.c:151-153, the sample's vertical;
+ *                                                                  of la, lo * M_PI / 180.]
+ *             c = U0*(q0 - g0) + U1*(q1 - g1) + U2*(q2 - g2);     (metres above the layer's top; < 0: below it)
+ *             if (c < best) { best = c; best_k = k + 1; }         (ties to the smallest k; a NaN never wins)
+ *     }
+ *     sample[i] = best_k;  if (n_data) n_data[i] = count;
+ *     if (best_k) clearance[i] = best;                            (else it keeps its value)
+ *
+ * The pair sees each other over that layer iff clearance[i] >= 0 -- or above a margin of the
+ * caller's own (a Fresnel zone, the mast that would make a blocked pair visible); sample[i] says
+ * where along the chord it comes closest, n_data[i] how many samples had data under them.  The
+ * fractions are not checked: values outside [0, 1] extrapolate the chord, repeated values are
+ * legal; at 0 and 1 the clearance is the end point's own height.  p == t is not special.  The
+ * arithmetic is the strict one; only the sample's turtle_ecef_to_geodetic honours
+ * turtle_amd_math_set, exactly as a sample of turtle_stepper_viewshed_n does: FAST takes latitude
+ * and altitude from the fast transform and the longitude from the closed form's atan2, which keeps
+ * n_data the reference's beside seams and missing tiles.
+ *
+ * BAD_ADDRESS: stepper, observer, target, fraction, clearance or sample NULL (n_data may be).
+ * DOMAIN_ERROR: layer_index outside the stepper's layers ("no valid data"), an unknown space,
+ * unknown flag bits, PAIRED with m != n, a number of lines beyond an int; all of them before a
+ * device is touched, changing nothing.  n, m or n_fractions <= 0 does nothing and succeeds.  Every
+ * tile of every stack has to be in memory, as for turtle_stepper_horizon_n: the call loads what is
+ * missing and fails with DOMAIN_ERROR where a stack's stack_size is below its number of tiles;
+ * turtle_amd_stepper_rounds reports 1 afterwards.  In DEVICE space the call only queues work. */
+TURTLE_API enum turtle_return turtle_stepper_clearance_n(
+    struct turtle_stepper * stepper, long n, const double * observer /* [n][3] */,
+    long m, const double * target /* [m][3] */,
+    int n_fractions, const double * fraction /* [n_fractions], shared by all lines */,
+    int layer_index, int flags,
+    double * clearance /* [n][m] (or [n]), in / out */,
+    int * sample /* same shape, mandatory */,
+    int * n_data /* same shape, or NULL */, int space);
+
 /* Flags of turtle_stepper_step_n. */
 enum turtle_amd_step_flags {
         /* On entry altitude[], elevation[][2] and index[][2] hold the values a

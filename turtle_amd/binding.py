@@ -16,6 +16,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 HOST, DEVICE = 0, 1
 STEP_RESUME = 1
+CLEARANCE_PAIRED = 1
 TRACE_RESUME = 1
 SCATTER_START = 1
 RESAMPLE_CLAMP = 1
@@ -696,6 +697,29 @@ class Stepper:
         _check(lib().turtle_stepper_viewshed_n(
             self.h, C.c_long(n), _ptr(pos), n_az, _ptr(az), n_d, _ptr(ds), layer, C.c_double(target_height),
             _ptr(res["visible"]), _ptr(res.get("sine")), _ptr(res.get("horizon")), _ptr(res.get("n_visible")), sp))
+        return res
+
+    def clearance(self, observer, target, fraction, layer=0, paired=False, out=None, want=("n_data",)):
+        """turtle_stepper_clearance_n -> dict(clearance, sample[, n_data]), each (n, m), or (n,)
+        where `paired`: for every line from an observer to a target (line r from observer r to
+        target r where paired) the least height (metres) of the straight chord above the top of
+        `layer` over its samples at the fractions `fraction` of the chord, the 1-based number of
+        that sample and the number of samples with data under them.  The pair sees each other iff
+        clearance >= 0.  Lines without a sample that has data get sample 0 and keep what `out`
+        held (a prefilled clearance, or a dict with one), zeros without one."""
+        sp = _space_of(observer, target, fraction)
+        obs, tgt, fr = _as(observer, sp).reshape(-1, 3), _as(target, sp).reshape(-1, 3), _as(fraction, sp).reshape(-1)
+        n, m = obs.shape[0], tgt.shape[0]
+        shape = (n,) if paired else (n, m)
+        cl = out.get("clearance") if isinstance(out, dict) else out
+        if cl is None:
+            cl = _new(shape, sp, like=obs, zero=True)
+        res = dict(clearance=cl, sample=_new(shape, sp, np.int32, like=obs, zero=True))
+        if "n_data" in want:
+            res["n_data"] = _new(shape, sp, np.int32, like=obs, zero=True)
+        _check(lib().turtle_stepper_clearance_n(
+            self.h, C.c_long(n), _ptr(obs), C.c_long(m), _ptr(tgt), fr.shape[0], _ptr(fr), layer,
+            CLEARANCE_PAIRED if paired else 0, _ptr(cl), _ptr(res["sample"]), _ptr(res.get("n_data")), sp))
         return res
 
     def step(self, position, direction=None, resume=None, outputs=True):

@@ -27,6 +27,8 @@
  *                   line's samples of a layer's top (turtle_stepper_horizon_n)
  *   k_viewshed      which samples of those lines the observer sees: a wave-wide prefix maximum
  *                   over chunks of 64 samples (turtle_stepper_viewshed_n)
+ *   k_clearance     the least height of the chord from an observer to a target above a layer's
+ *                   top, one wave per line (turtle_stepper_clearance_n)
  *   k_step          batch turtle_stepper_step [ref stepper.c:780-875]: the sample and
  *   k_step_fast     the tentative step; rays that crossed a boundary are listed
  *                   (k_step_fast: the fast-math body of the one-map / one-stack
@@ -584,6 +586,69 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
                         }
                 }
                 if ((n_visible != nullptr) && (lane == 0)) n_visible[i] = count;
+        }
+}
+
+/* turtle_stepper_clearance_n: the minimum clearance of the straight chord from an observer to a
+ * target above a layer's top.  One WAVE per item (i = r * n_t + t, or i = r with PAIRED), four
+ * items a block, as in k_horizon; lane l takes the samples k = l, l + 64, ... at the fractions
+ * fraction[k] of the chord and keeps its own (least clearance, k + 1, number of samples with
+ * data); the wave reduces the 64 pairs with a butterfly of shuffles under the order "smaller
+ * clearance, then smaller k", which is what the strict `<` of the sequential loop gives, sums the
+ * counts, and lane 0 writes.  The chord's ends and their difference are wave-uniform.  A sample's
+ * transform is d_sight_sample's with CLOSED_LON (FAST: latitude from the fast transform, longitude
+ * from the closed form's atan2, so that a sample has data where the reference says it has);
+ * everything else is the strict arithmetic.  The ground under the sample (d_from_geodetic) and the
+ * sample's vertical (d_enu's u) are written with the same expressions of the same latitude and
+ * longitude: one set of sines and cosines serves both.  No paging: the geometry is resident. */
+template <int MODE, bool FAST>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_clearance(tamd_view v, int n_items, int n_t, int paired,
+    int n_f, const double * __restrict__ observer, const double * __restrict__ target,
+    const double * __restrict__ fraction, int layer, double * __restrict__ clearance,
+    int * __restrict__ sample, int * __restrict__ n_data)
+{
+        OneCtx ctx;
+        d_load_ctx<MODE, false>(v, ctx);
+        const int lane = (int)(threadIdx.x & 63);
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        for (long i = blockIdx.x * 4L + wave; i < (long)n_items; i += (long)gridDim.x * 4L) {
+                const long r = paired ? i : i / n_t;
+                const long t = paired ? i : i - r * n_t;
+                const double p0 = observer[3 * r], p1 = observer[3 * r + 1], p2 = observer[3 * r + 2];
+                const double d0 = target[3 * t] - p0, d1 = target[3 * t + 1] - p1, d2 = target[3 * t + 2] - p2;
+
+                double best = HUGE_VAL;
+                int best_k = 0, count = 0;
+                for (int k = lane; k < n_f; k += 64) {
+                        const double f = fraction[k];
+                        const double x = p0 + f * d0, y = p1 + f * d1, z = p2 + f * d2;
+                        double la, lo, al, top;
+                        if (FAST) {
+                                f_to_geodetic(x, y, z, la, lo, al);
+                                if ((x != 0.) || (y != 0.)) lo = atan2(y, x) * 180. / kPi;
+                        } else
+                                d_to_geodetic(x, y, z, la, lo, al);
+                        if (!d_layer_top<MODE>(v, ctx, layer, la, lo, top)) continue;
+                        count++;
+                        double g0, g1, g2, e[3], nn[3], u[3];
+                        d_from_geodetic(la, lo, top + 0., g0, g1, g2);
+                        d_enu(la, lo, e, nn, u);
+                        const double c = u[0] * (x - g0) + u[1] * (y - g1) + u[2] * (z - g2);
+                        if (c < best) best = c, best_k = k + 1; /* (a NaN never wins) */
+                }
+                for (int off = 32; off > 0; off >>= 1) {
+                        const double o_best = __shfl_xor(best, off, 64);
+                        const int o_k = __shfl_xor(best_k, off, 64);
+                        count += __shfl_xor(count, off, 64);
+                        /* (a lane without a winner holds (+inf, 0): it never wins, and loses to any) */
+                        if ((o_best < best) || ((o_best == best) && (o_k != 0) && (o_k < best_k)))
+                                best = o_best, best_k = o_k;
+                }
+                if (lane == 0) {
+                        sample[i] = best_k;
+                        if (n_data != nullptr) n_data[i] = count;
+                        if (best_k != 0) clearance[i] = best;
+                }
         }
 }
 
@@ -3092,6 +3157,19 @@ extern "C" int tamd_k_viewshed(struct tamd_view view, int n_items, int n_azimuth
                 return launch_blocks("k_viewshed", k_viewshed<decltype(mode)::value, decltype(fast)::value>, grid, 0,
                     view, n_items, n_azimuths, n_distances, pos, azimuth, distance, layer, target_height, visible,
                     sine, horizon, n_visible);
+        });
+}
+
+/* chords, not fans: n_items lines from observers to targets (item r * n_targets + t, or r alone
+ * where paired), the minimum over n_fractions samples of each */
+extern "C" int tamd_k_clearance(struct tamd_view view, int n_items, int n_targets, int paired, int n_fractions,
+    const double * observer, const double * target, const double * fraction, int layer, double * clearance,
+    int * sample, int * n_data)
+{
+        return launch_sight(view, n_items, n_targets, n_fractions, [&](auto mode, auto fast, auto grid) {
+                return launch_blocks("k_clearance", k_clearance<decltype(mode)::value, decltype(fast)::value>, grid, 0,
+                    view, n_items, n_targets, paired, n_fractions, observer, target, fraction, layer, clearance,
+                    sample, n_data);
         });
 }
 

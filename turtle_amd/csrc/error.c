@@ -117,6 +117,7 @@ const char * turtle_error_function(turtle_function_t * caller)
         NAME(turtle_stepper_normal_n);
         NAME(turtle_stepper_horizon_n);
         NAME(turtle_stepper_viewshed_n);
+        NAME(turtle_stepper_clearance_n);
         NAME(turtle_stepper_step_n);
         NAME(turtle_stepper_walk_n);
         NAME(turtle_stepper_trace_n);

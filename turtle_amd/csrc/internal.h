@@ -124,6 +124,13 @@ int tamd_k_horizon(struct tamd_view view, int n_items, int n_azimuths, int n_dis
 int tamd_k_viewshed(struct tamd_view view, int n_items, int n_azimuths, int n_distances,
     const double * pos, const double * azimuth, const double * distance, int layer, double target_height,
     signed char * visible, double * sine, double * horizon, int * n_visible);
+/* the clearance of chords (turtle_stepper_clearance_n): item r * n_targets + t is the line from
+ * observer r to target t, or item r the line to target r where `paired`; over RESIDENT geometry
+ * only; items without a sample that has data get sample 0 and keep their clearance; n_data
+ * [n_items] where it is wanted (NULL: not) */
+int tamd_k_clearance(struct tamd_view view, int n_items, int n_targets, int paired, int n_fractions,
+    const double * observer, const double * target, const double * fraction, int layer, double * clearance,
+    int * sample, int * n_data);
 int tamd_k_step(struct tamd_view view, long n, double * pos,
     const double * dir, double * lat, double * lon, double * alt,
     double * elev, double * step, int * index, int flags, struct tamd_paging pg);

@@ -922,6 +922,66 @@ enum turtle_return turtle_stepper_viewshed_n(struct turtle_stepper * stepper, lo
         return sight_run(&error_, &a.lines, stepper, space, &viewshed_resident, &a);
 }
 
+/* The chords of turtle_stepper_clearance_n are not sight_begin's fans (no azimuths, no distances):
+ * the call has a begin of its own, with the same checks in the same order, and shares the stage,
+ * the residency and sight_run.  Of `lines`: n_azimuths holds the targets of an observer (1 where
+ * paired), n_distances the fractions; azimuth and distance stay NULL. */
+struct clearance_args {
+        struct sight_lines lines;
+        int paired;
+        void *target, *fraction, *clearance, *sample, *n_data;
+};
+
+static int clearance_resident(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
+{
+        struct clearance_args * a = p;
+        struct sight_lines * l = &a->lines;
+        (void)pg, (void)round;
+        if ((l->paged = stepper_is_paged(stepper))) return 0; /* (a tile another thread took meanwhile) */
+        return tamd_k_clearance(stepper->view, l->n_items, l->n_azimuths, a->paired, l->n_distances, l->pos,
+            a->target, a->fraction, l->layer, a->clearance, a->sample, a->n_data);
+}
+
+enum turtle_return turtle_stepper_clearance_n(struct turtle_stepper * stepper, long n,
+    const double * observer, long m, const double * target, int n_fractions, const double * fraction,
+    int layer_index, int flags, double * clearance, int * sample, int * n_data, int space)
+{
+        TAMD_ERROR_INIT(&turtle_stepper_clearance_n);
+        if ((stepper == NULL) || (observer == NULL) || (target == NULL) || (fraction == NULL) ||
+            (clearance == NULL) || (sample == NULL))
+                return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
+        if ((layer_index < 0) || (layer_index >= stepper->n_layers))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "no valid data");
+        if ((space != TURTLE_AMD_HOST) && (space != TURTLE_AMD_DEVICE))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid space (%d)", space);
+        if (flags & ~TURTLE_AMD_CLEARANCE_PAIRED)
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid flags (%d)", flags);
+        const int paired = (flags & TURTLE_AMD_CLEARANCE_PAIRED) != 0;
+        if (paired && (m != n))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
+                    "paired lines need as many targets as observers (%ld observers, %ld targets)", n, m);
+        if ((n <= 0) || (m <= 0) || (n_fractions <= 0)) return TURTLE_RETURN_SUCCESS;
+        if (paired ? (n > (long)INT_MAX) : (n > (long)INT_MAX / m))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR,
+                    "too many lines (%ld observers, %ld targets): the items of a call are numbered by ints", n, m);
+        const enum turtle_return loaded =
+            stepper_load_all(stepper, &error_, turtle_error_function(error_.function), "reads");
+        if (loaded != TURTLE_RETURN_SUCCESS) return loaded;
+        struct clearance_args a = { 0 };
+        struct sight_lines * l = &a.lines;
+        a.paired = paired;
+        l->n_items = paired ? (int)n : (int)(n * m), l->n_azimuths = paired ? 1 : (int)m;
+        l->n_distances = n_fractions, l->layer = layer_index;
+        const size_t items = (size_t)l->n_items;
+        tamd_stage_add(&l->stage, observer, 3 * (size_t)n * sizeof(double), TAMD_IN, &l->pos);
+        tamd_stage_add(&l->stage, target, 3 * (size_t)m * sizeof(double), TAMD_IN, &a.target);
+        tamd_stage_add(&l->stage, fraction, (size_t)n_fractions * sizeof(double), TAMD_IN, &a.fraction);
+        tamd_stage_add(&l->stage, clearance, items * sizeof(double), TAMD_INOUT, &a.clearance); /* lines without */
+        tamd_stage_add(&l->stage, sample, items * sizeof(int), TAMD_OUT, &a.sample);          /* a sample keep theirs */
+        tamd_stage_add(&l->stage, n_data, items * sizeof(int), TAMD_OUT, &a.n_data);
+        return sight_run(&error_, l, stepper, space, &clearance_resident, &a);
+}
+
 /* Grow-only scratch of the batch calls: 4 n ints (the rays a trace hands from
  * pass to pass, the rays whose step crossed a boundary and what they found
  * there / the rays a batch of steps defers to its bisection pass; the step
