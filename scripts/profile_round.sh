@@ -12,7 +12,7 @@ passes=${4:-A B C D}
 math=${MATH:-fast}
 export TURTLE_AMD_MATH=$math
 WL="--workload $wl --rays $rays --also none --in-flight 1"   # one batch at a time: the kernels alone on the GPU
-kernel="k_trace|k_cross"; [ "$wl" = c5 ] && kernel=k_walk
+kernel="k_trace|k_first|k_cross"; [ "$wl" = c5 ] && kernel=k_walk
 if [ "$wl" = c5_step_n ]; then
   # the walk through turtle_stepper_step_n, the caller's directions: two kernels a generation
   WL="--workload c5 --step-n 64 --rays $rays --also none --in-flight 1"; kernel="k_step|k_bisect"

@@ -36,6 +36,7 @@
  *   k_bisect        ... and bisected here, packed [ref stepper.c:836-864]
  *   k_gradient, k_project   batch gradients and map projections
  *   k_trace         persistent-wave trace-to-boundary loop (the hot kernel)
+ *   k_first         a fast trace's first closed-form steps, flat: a ray a lane
  *   k_isotropic     Philox-4x32-10 isotropic directions (scattering harness)
  *   k_tally         hit counts + path-length histogram (uint64, exact)
  */
@@ -2185,6 +2186,194 @@ k_trace(tamd_view v, long n,
             ph, stats, queue);
 }
 
+/* The first pass of a fast trace over one map or one stack, flat: a ray a lane, no queue.
+ *
+ * Nearly every ray of a batch outlives the hand-over at step `park` (C2: 999 819 of 10^6 take
+ * more than 32 steps), so what phase A does is the same in every lane -- the origin sample, `park`
+ * closed-form steps, the hand-over -- and the persistent kernel's refill queue, its `drain` and the
+ * branches of its state machine serve a divergence that is not there: they cost it a third of its
+ * vector instructions (scalar registers spilled to vector lanes and read back inside the step).
+ * Here a wave loads its 64 rays, steps them `park` times (or until none is left) and hands over
+ * ALL AT ONCE: the rays that ended write their results, the others go on the hand-over list or
+ * on the crossings' list L1, exactly as trace_body's phase A leaves them -- the same functions on
+ * the same values in the same order, so every result and every total is the same bit for bit;
+ * only the order of the lists differs, as it does from run to run anyway.  The places on a list
+ * are reserved once per BLOCK (its four waves park at the same moment: a prefix in LDS, then at
+ * most three atomics), not per wave.
+ * run_trace launches it where the rule there holds; everywhere else k_trace<..., MODEL = false>. */
+struct FirstPass {
+        int park;               /* the hand-over's step count: 0 < park < max_steps */
+        int mark_at;            /* the sorted hand-over, as PhaseIO's: */
+        float long_if;
+        int * parked;
+        ull * n_parked, * n_parked_back; /* (n_parked_back NULL: one end) */
+        unsigned char * sort_key;        /* (or NULL) */
+        CrossList cross;                 /* L1 */
+        /* rays in an order of the library's own (or NULLs: see PhaseIO) */
+        const double * pos_in, * dir_in;
+        const int * index_in;
+        double * dir_copy;
+};
+
+/* WAVES: the most waves a SIMD may hold (8: as many as the registers allow; see first_pass_waves) */
+template <int MODE, int WAVES>
+__global__ void __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(1, WAVES)))
+k_first(tamd_view v, long n, double * __restrict__ pos, const double * __restrict__ dir, int max_steps,
+    int * __restrict__ index, double * __restrict__ length, int * __restrict__ n_steps, int flags,
+    FirstPass fp, RayOut out, ull * __restrict__ stats)
+{
+        __shared__ unsigned wave_n[4][3]; /* [wave][list]: front, back, crossings */
+        __shared__ ull block_base[3];
+        OneCtx ctx;
+        d_load_ctx<MODE, true>(v, ctx);
+        CellCache cell = { ~0u, 0u, 0u, -1, nullptr };
+        const int wave = (int)(threadIdx.x >> 6);
+        ull my_rays = 0, my_steps = 0, my_samples = 0, my_capped = 0;
+
+        /* (block-uniform: every thread of a block meets the barriers below) */
+        for (long first = blockIdx.x * 256L; first < n; first += gridDim.x * 256L) {
+                const long ray = first + threadIdx.x;
+                const bool have = ray < n;
+                double bx = 0, by = 0, bz = 0, dx = 0, dy = 0, dz = 0, len = 0, ds = 0, d0 = 0;
+                int m = -1, k = -1, bm = -1, bk = -1, count = 0;
+                bool done = false, crossed = false;
+                if (have) {
+                        /* ---- the ray ---- */
+                        int given = -1;
+                        if (fp.dir_copy != nullptr) {
+                                const long src = out.order_of[ray];
+                                bx = fp.pos_in[3 * src], by = fp.pos_in[3 * src + 1], bz = fp.pos_in[3 * src + 2];
+                                dx = fp.dir_in[3 * src], dy = fp.dir_in[3 * src + 1], dz = fp.dir_in[3 * src + 2];
+                                fp.dir_copy[3 * ray] = dx, fp.dir_copy[3 * ray + 1] = dy, fp.dir_copy[3 * ray + 2] = dz;
+                                if (flags & TRACE_CARRY_MEDIUM) {
+                                        given = fp.index_in[2 * src];
+                                        index[2 * ray] = given, index[2 * ray + 1] = fp.index_in[2 * src + 1];
+                                }
+                        } else {
+                                bx = pos[3 * ray], by = pos[3 * ray + 1], bz = pos[3 * ray + 2];
+                                dx = dir[3 * ray], dy = dir[3 * ray + 1], dz = dir[3 * ray + 2];
+                                if (flags & TRACE_CARRY_MEDIUM) given = index[2 * ray];
+                        }
+                        /* ---- the origin sample (trace_body's INIT) ---- */
+                        Sample s;
+                        d_sample<MODE, true>(v, ctx, bx, by, bz, s, &cell);
+                        my_samples++;
+                        m = s.m, k = s.k;
+                        ds = (m >= 0) ? d_step_length(v, s.alt, s.e0, s.e1, m) : 0.;
+                        if ((flags & TRACE_CARRY_MEDIUM) && (m >= 0)) {
+                                /* (the given medium wins: see trace_body) */
+                                if ((given >= 0) && (given <= v.n_layers) && (given != m)) {
+                                        m = given;
+                                        ds = v.resolution;
+                                }
+                        }
+                        done = (m < 0) || (count >= max_steps);
+                        if (fp.mark_at == 0) d0 = ds;
+                }
+                /* ---- at most `park` closed-form steps (trace_body's CROSS bookkeeping) ---- */
+                bool live = have && !done;
+                for (int trip = 0; trip < fp.park; trip++) {
+                        if (__ballot(live) == 0) break;
+                        if (live) {
+                                const double qx = d_along<true>(bx, dx, ds), qy = d_along<true>(by, dy, ds),
+                                    qz = d_along<true>(bz, dz, ds);
+                                Sample s;
+                                d_sample<MODE, true>(v, ctx, qx, qy, qz, s, &cell);
+                                my_samples++;
+                                const bool same = (s.m == m);
+                                const double ds_next = d_step_length(v, s.alt, s.e0, s.e1, s.m);
+                                bx = qx, by = qy, bz = qz;
+                                crossed = !same;
+                                bm = s.m, bk = s.k;
+                                len = same ? len + ds : len;
+                                k = same ? s.k : k;
+                                ds = same ? ds_next : ds; /* a crossing keeps the tentative length */
+                                count += same ? 1 : 0;
+                                const bool capped = same & (count >= max_steps);
+                                done = capped;
+                                my_capped += capped ? 1 : 0;
+                                d0 = (same & (count == fp.mark_at)) ? ds : d0;
+                                live = same & !capped & (count < fp.park);
+                        }
+                }
+                /* ---- the hand-over: the whole block, once ---- */
+                const bool park = have & !done & !crossed; /* (count == fp.park: the loop's bound) */
+                bool back = false;
+                if (park && (fp.n_parked_back != nullptr) && (count > fp.mark_at)) {
+                        /* (the long-ray predictor: see where trace_body parks) */
+                        const float shrink = __logf((float)d0 / (float)ds);
+                        const float togo = __logf((float)ds / (float)v.resolution);
+                        back = (shrink > 0.f) && !(togo * (float)(count - fp.mark_at) > fp.long_if * shrink);
+                }
+                const ull bmask = __ballot(back);
+                const ull fmask = __ballot(park) & ~bmask;
+                const ull cmask = __ballot(crossed);
+                if ((threadIdx.x & 63) == 0) {
+                        wave_n[wave][0] = (unsigned)__popcll(fmask);
+                        wave_n[wave][1] = (unsigned)__popcll(bmask);
+                        wave_n[wave][2] = (unsigned)__popcll(cmask);
+                }
+                __syncthreads();
+                if (threadIdx.x < 3) {
+                        const ull sum = (ull)wave_n[0][threadIdx.x] + wave_n[1][threadIdx.x] + wave_n[2][threadIdx.x] +
+                            wave_n[3][threadIdx.x];
+                        ull * const counter = (threadIdx.x == 0) ? fp.n_parked :
+                            ((threadIdx.x == 1) ? fp.n_parked_back : fp.cross.count);
+                        block_base[threadIdx.x] = (sum != 0) ? atomicAdd(counter, sum) : 0;
+                }
+                __syncthreads();
+                ull base[3];
+                for (int l = 0; l < 3; l++) {
+                        base[l] = block_base[l];
+                        for (int w = 0; w < 3; w++) base[l] += (w < wave) ? wave_n[w][l] : 0u;
+                }
+                __syncthreads(); /* (the next chunk writes wave_n again) */
+                if (done) {
+                        if (out.order_of != nullptr) { /* to the caller's arrays, the ray's place there */
+                                const long o = out.order_of[ray];
+                                out.pos[3 * o] = bx, out.pos[3 * o + 1] = by, out.pos[3 * o + 2] = bz;
+                                out.index[2 * o] = m, out.index[2 * o + 1] = k;
+                                out.length[o] = len;
+                                out.n_steps[o] = count;
+                        } else {
+                                pos[3 * ray] = bx, pos[3 * ray + 1] = by, pos[3 * ray + 2] = bz;
+                                index[2 * ray] = m, index[2 * ray + 1] = k;
+                                length[ray] = len;
+                                n_steps[ray] = count;
+                        }
+                        my_rays++;
+                        my_steps += (ull)count;
+                }
+                if (park | crossed) {
+                        if (park) {
+                                const long place = back ? n - 1 - (long)(base[1] + lane_rank(bmask)) :
+                                    (long)(base[0] + lane_rank(fmask));
+                                fp.parked[place] = (int)ray;
+                                if (fp.sort_key != nullptr) {
+                                        /* (how shallow the ray goes: see where trace_body parks) */
+                                        const double up = __builtin_fma(dx, bx, __builtin_fma(dy, by, dz * bz)) *
+                                            __builtin_amdgcn_rsq(__builtin_fma(bx, bx, __builtin_fma(by, by, bz * bz)));
+                                        const double scaled = fmin(fabs(up) * 1024., 253.);
+                                        fp.sort_key[place] = back ? (unsigned char)255 : (unsigned char)scaled;
+                                }
+                        } else {
+                                const long place = (long)(base[2] + lane_rank(cmask));
+                                fp.cross.ray[place] = (int)ray;
+                                fp.cross.ds[place] = ds;
+                                fp.cross.other[place] = cross_pack(bm, bk);
+                        }
+                        /* (a crossing: B is the tentative point; m, k the medium it left) */
+                        pos[3 * ray] = bx, pos[3 * ray + 1] = by, pos[3 * ray + 2] = bz;
+                        index[2 * ray] = m, index[2 * ray + 1] = k;
+                        length[ray] = len;
+                        n_steps[ray] = count;
+                        my_steps += (ull)count;
+                }
+        }
+        block_tally(stats, my_rays, my_steps, my_samples, my_capped);
+}
+
 /* The crossings of a trace, every lane busy: for each listed ray the bracket
  * [-ds, 0] behind its tentative point q is narrowed below 1e-8 m [ref
  * stepper.c:832-864] -- by halving, on closed-form samples, in the reference's
@@ -3423,6 +3612,49 @@ static int cross_tail_on(long n)
 /* phase A hands over when its queue is dry and a wave is down to this many rays (PhaseIO.drain_lanes;
  * 0: never, as in the passes that have nobody to hand over to): 64, so any wave does */
 constexpr int kDrainLanes = 64;
+/* Does the flat kernel (k_first) take the closed-form pass of a fast trace over one map or one
+ * stack?  Where that pass is `park` uniform steps and a hand-over: the first round (a later round
+ * of a paged trace takes rays at any step count), nothing paged (a ray may have to leave for a
+ * tile at any sample), a hand-over within the kernel's bounded loop, and -- the caller's part -- lists
+ * to hand over on and a step cap beyond the hand-over.  Everything else is k_trace's, as before.
+ * The same bits either way (tests/test_gpu_first_pass.py).
+ * TURTLE_AMD_FIRST_PASS=0 / 1: never / wherever the rule allows (unset: the rule). */
+static bool first_pass_flat(int park, bool again, const Paging & pg)
+{
+        static Knob knob = { "TURTLE_AMD_FIRST_PASS", -1 };
+        if (knob.get() == 0) return false;
+        return !again && (pg.faulted == nullptr) && (park > 0) && (park <= 64);
+}
+/* The waves a SIMD holds of it: three, while the rays come as the caller has them -- the gathers
+ * of a wave then go all over the terrain, and more waves only take each other's lines out of the
+ * caches (measured, one map, kernel time in us at 5 -- what the registers allow -- / 4 / 3 / 2 waves:
+ * 1 M rays 475 / 447 / 420 / 488; 0.5 M 244 / 237 / 227; 1.5 M 696 / 648 / 623; 2 M 919 / 847 / 822;
+ * 0.25 M 126 / 127 / 131; a 4 x 4 stack, 1 M rays, at 4 -- what fits there -- / 3 / 2: 795 / 700 / 656, the
+ * persistent kernel 792); as many as fit once the rays are in the order of where they start
+ * (spatial_order(); 3 M rays 1104 / 1117 / 1190; 12.5 M 4634 / 4735 / 5004; a stack, 10 M: 4329 at
+ * 4, 4514 at 3, 5298 at 2).  TURTLE_AMD_FIRST_WAVES=3 / 8: three / as many as fit, always. */
+static int first_pass_waves(bool ordered)
+{
+        static Knob knob = { "TURTLE_AMD_FIRST_WAVES", -1 };
+        if (knob.get() > 0) return (knob.get() <= 3) ? 3 : 8;
+        return ordered ? 8 : 3;
+}
+/* Its grid: a block for every 256 rays (C2: 474 us; as the other flat kernels' grid -- grid_for: eight
+ * blocks a CU at the most, each taking chunks of 256 rays in turn, TURTLE_AMD_FIRST_GRID=0 -- 485 us; as
+ * 2 / 3 / 4 / 5 / 6 blocks a CU taking chunks in turn 519 / 446 / 482 / 494 / 515: what counts there is
+ * the waves a SIMD holds, see above). */
+template <int MODE>
+static int launch_first(struct tamd_view view, long n, double * pos, const double * dir, int max_steps,
+    int * index, double * length, int * n_steps, int flags, const FirstPass & fp, const RayOut & out, ull * stats)
+{
+        static Knob grid = { "TURTLE_AMD_FIRST_GRID", 1 };
+        if (tamd_dev_init()) return 1;
+        const unsigned blocks = (grid.get() == 0) ? (unsigned)grid_for(n, 256) : (unsigned)((n + 255) / 256);
+        return with_constant<3, 8>(first_pass_waves(out.order_of != nullptr), [&](auto waves) {
+                return launch_blocks("k_first", k_first<MODE, decltype(waves)::value>, blocks, 0, view, n, pos, dir,
+                    max_steps, index, length, n_steps, flags, fp, out, stats);
+        });
+}
 /* the room behind the lists of a trace (internal.h, TAMD_TRACE_SORT_ROOM), on a 256-byte boundary */
 static char * sort_room_of(int * parked, long n)
 {
@@ -3568,7 +3800,19 @@ static int run_trace(struct tamd_view view, long n, double * pos, const double *
                         HIP_TRY(hipMemsetAsync(keys.Current(), 0xFE, (size_t)n, g_stream));
                 }
         }
-        if (first_pass(Fast(), a)) return 1;
+        bool flat = false;
+        if constexpr (MODE != TAMD_MODE_GENERIC) {
+                if (first_pass_flat(park, again, pg)) {
+                        /* (the closed-form pass of a fast, listed, uncapped first round: k_first) */
+                        flat = true;
+                        const FirstPass fp = { park, a.mark_at, a.long_if, parked, a.n_parked, a.n_parked_back,
+                                a.sort_key, cross, a.pos_in, a.dir_in, a.index_in, a.dir_copy };
+                        if (launch_first<MODE>(view, n, pos, dir, max_steps, index, length, n_steps, flags, fp, out,
+                                stats))
+                                return 1;
+                }
+        }
+        if (!flat && first_pass(Fast(), a)) return 1;
         if (sorting) {
                 if (hipcub::DeviceRadixSort::SortPairs(sort_temp, temp_bytes, keys, ids, (int)n, 0, 8, g_stream) !=
                     hipSuccess)
