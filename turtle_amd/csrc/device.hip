@@ -51,6 +51,7 @@
 
 #include "device_ctx.h"
 #include "internal.h" /* includes turtle_amd_device.h: the device functions and the tables */
+#include "trace_room.h"
 
 using namespace turtle_amd_device;
 
@@ -707,7 +708,7 @@ struct CrossList {
  * equals the waves of the grid nobody adds to L1 any more, and a wave that has run out of rays
  * locates L1 by tickets of 64 entries drawn from l1_next.  k_cross takes the rest.  NULL: one
  * list, all of it left to k_cross. */
-constexpr int kQ = 16; /* words between two counters of a trace: see run_trace */
+constexpr int kQ = TAMD_TRACE_COUNTER_STRIDE; /* words between two counters of a trace (internal.h) */
 constexpr int kQTail = 4 * kQ;
 struct CrossTail {
         ull * words; /* the three counters, kQ words apart */
@@ -3476,18 +3477,26 @@ static int launch_trace(struct tamd_view view, long n, bool n_on_device, double 
 #undef TRACE_ARGS
 }
 
+/* the arrays the passes of a trace work in: the caller's, or the library's own (order_rays) */
+struct TraceRays {
+        double * pos;
+        const double * dir;
+        int * index;
+        double * length;
+        int * n_steps;
+};
+
 /* the crossings the passes listed (their number is on the device: a grid for
  * all of n, striding over whatever there is) */
 template <int MODE, bool FAST>
-static int launch_cross(struct tamd_view view, long n, double * pos, const double * dir, int * index,
-    double * length, int * n_steps, CrossList cross, Paging pg, ull * stats,
-    RayOut out = { nullptr, nullptr, nullptr, nullptr, nullptr }, CrossTail front = { nullptr })
+static int launch_cross(struct tamd_view view, long n, const TraceRays & rays, CrossList cross, Paging pg,
+    ull * stats, RayOut out = { nullptr, nullptr, nullptr, nullptr, nullptr }, CrossTail front = { nullptr })
 {
         constexpr bool CAN_PAGE = (MODE != TAMD_MODE_ONE_MAP);
         const bool paged = CAN_PAGE && (pg.faulted != nullptr);
         const auto kernel = paged ? k_cross<MODE, FAST, CAN_PAGE> : k_cross<MODE, FAST, false>;
-        return launch_blocks("k_cross", kernel, persistent_blocks(kernel, n), 0, view, pos, dir, index, length,
-            n_steps, cross, pg, stats, out, front, n);
+        return launch_blocks("k_cross", kernel, persistent_blocks(kernel, n), 0, view, rays.pos, rays.dir, rays.index,
+            rays.length, rays.n_steps, cross, pg, stats, out, front, n);
 }
 
 /* ---- the launch policy ---------------------------------------------------
@@ -3655,11 +3664,152 @@ static int launch_first(struct tamd_view view, long n, double * pos, const doubl
                     max_steps, index, length, n_steps, flags, fp, out, stats);
         });
 }
-/* the room behind the lists of a trace (internal.h, TAMD_TRACE_SORT_ROOM), on a 256-byte boundary */
-static char * sort_room_of(int * parked, long n)
+
+/* ---- a trace's passes ------------------------------------------------------
+ *
+ * Where their lists and arrays are: trace_room.h; their counters: internal.h (enum
+ * tamd_trace_counter). */
+
+static ull * counter_of(ull * queue, enum tamd_trace_counter c) { return queue + (int)c * kQ; }
+/* (the lined pass is given B's queue and finds the tail's words from there: CrossTail) */
+static_assert(((int)TAMD_TRACE_TAIL_N_DRY - (int)TAMD_TRACE_QUEUE_B) * kQ == kQTail,
+    "CrossTail.n_dry is kQTail words behind the lined pass's queue");
+static_assert(((int)TAMD_TRACE_TAIL_L1_NEXT == (int)TAMD_TRACE_TAIL_N_DRY + 1) &&
+        ((int)TAMD_TRACE_TAIL_L2_COUNT == (int)TAMD_TRACE_TAIL_N_DRY + 2),
+    "CrossTail.l1_next and .l2_count follow n_dry, kQ words apart");
+
+/* A radix sort (hipCUB) of n (key, ray id) pairs in a trace's scratch: the ids in the hand-over
+ * list's place and the keys beside them, each with its second buffer.  fits() asks what the sort
+ * needs and says whether that is within its room; run() sorts, and Current() of both is the result. */
+template <class KEY>
+struct RoomSort {
+        static_assert(sizeof(KEY) <= sizeof(int), "a key buffer holds an int a ray (trace_room.h)");
+        hipcub::DoubleBuffer<KEY> keys;
+        hipcub::DoubleBuffer<int> ids;
+        void * temp;
+        size_t temp_bytes;
+        int n, bits;
+        RoomSort(char * room, const tamd_trace_room & at, long n_, int bits_)
+            : keys(TAMD_ROOM_AT(KEY, room, at.keys), TAMD_ROOM_AT(KEY, room, at.keys_alt)),
+              ids(TAMD_ROOM_AT(int, room, at.parked), TAMD_ROOM_AT(int, room, at.ids_alt)),
+              temp(room + at.sort_temp), temp_bytes(0), n((int)n_), bits(bits_)
+        {
+        }
+        bool fits()
+        {
+                return (hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys, ids, n, 0, bits, g_stream) ==
+                           hipSuccess) &&
+                    (temp_bytes <= TAMD_TRACE_SORT_TEMP);
+        }
+        int run()
+        {
+                if (hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, ids, n, 0, bits, g_stream) != hipSuccess)
+                        return fail("hipcub::DeviceRadixSort", hipGetLastError());
+                return 0;
+        }
+};
+
+/* The rays in the order of where they start (k_ray_cells): keys and numbers into the sort's
+ * room, one pass of the radix sort.  The passes then WORK in that order -- a ray's state
+ * between the passes (position, medium, path length, step count, its direction) lives at its
+ * place in the ordered list, in arrays of the library's own -- while the caller's arrays are
+ * touched twice a ray: phase A reads a new ray from its place there, and whichever kernel
+ * ENDS a ray (k_cross for nearly all) writes its results to that place (RayOut); no pass of
+ * its own copies anything.  (Tried first: the passes working in the caller's arrays through
+ * the ordered list -- every hand-over then goes to a place of its own instead of next to
+ * its wave's: half the gain on C3, a loss on C4; and copies made by kernels of their own:
+ * 0.9 + 1.4 ms for C4's 12.5 M rays, more than the order gains there.)  Not over paged tiles
+ * (the pager's lists name rays by their place in the CALLER's arrays, round after round).
+ * Leaves everything as it is where the sort does not fit its room. */
+template <int MODE>
+static int order_rays(struct tamd_view view, long n, char * room, const tamd_trace_room & at, TraceRays & rays,
+    PhaseIO & a, PhaseIO & b, RayOut & out)
 {
-        const uintptr_t at = (uintptr_t)(parked + TAMD_TRACE_SORT_INTS * n);
-        return (char *)((at + 255) & ~(uintptr_t)255);
+        RoomSort<SPATIAL_KEY_T> sort(room, at, n, SPATIAL_BITS);
+        if (!sort.fits()) return 0;
+        hipLaunchKernelGGL(k_ray_cells<MODE>, dim3(grid_for(n, 256)), dim3(256), 0, g_stream, view, n, rays.pos,
+            sort.keys.Current(), sort.ids.Current());
+        LAUNCH_CHECK("k_ray_cells");
+        if (sort.run()) return 1;
+        /* the list must outlive the passes, which use its place and the sort's room again */
+        int * const kept = TAMD_ROOM_AT(int, room, at.order);
+        HIP_TRY(hipMemcpyAsync(kept, sort.ids.Current(), (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, g_stream));
+        out.order_of = kept, out.pos = rays.pos, out.index = rays.index, out.length = rays.length;
+        out.n_steps = rays.n_steps;
+        a.out = out, b.out = out;
+        a.pos_in = rays.pos, a.dir_in = rays.dir, a.index_in = rays.index;
+        a.dir_copy = TAMD_ROOM_AT(double, room, at.dir_s);
+        rays.pos = TAMD_ROOM_AT(double, room, at.pos_s), rays.dir = a.dir_copy;
+        rays.index = TAMD_ROOM_AT(int, room, at.index_s), rays.length = TAMD_ROOM_AT(double, room, at.length_s);
+        rays.n_steps = TAMD_ROOM_AT(int, room, at.n_steps_s);
+        return 0;
+}
+
+/* The hand-over of a first round (a later round of a paged trace takes rays at any step count:
+ * one end, unsorted).  The list is filled from both ends (sort_long_if(); PhaseIO).  And its front
+ * may be ORDERED: keys beside the list, a radix sort of the whole list's n places between
+ * the two passes -- places nobody filled carry a key (254) between the front's (0 .. 253) and the
+ * back's (255), so the front comes out first, in order, and the back stays at the far end, where
+ * the lined pass looks for it.  For batches small enough to be as long as their longest rays
+ * (sort_hand_over()).  Planned before phase A, which writes the keys ... */
+static int hand_over_plan(RoomSort<unsigned char> & sort, long n, bool again, ull * queue, double * ds_mark,
+    PhaseIO & a, PhaseIO & b, bool & sorting)
+{
+        const int long_if = sort_long_if();
+        sorting = false;
+        if (again || (long_if <= 0)) return 0;
+        a.n_parked_back = counter_of(queue, TAMD_TRACE_N_PARKED_BACK);
+        a.ds_mark = ds_mark, a.mark_at = a.park_after / 2, a.long_if = (float)long_if;
+        b.n_dev_back = a.n_parked_back;
+        sorting = sort_hand_over(n) && sort.fits();
+        if (!sorting) return 0;
+        a.sort_key = sort.keys.Current();
+        HIP_TRY(hipMemsetAsync(a.sort_key, 0xFE, (size_t)n, g_stream));
+        return 0;
+}
+/* ... and run behind it: the lined pass reads the ordered list */
+static int hand_over_sort(RoomSort<unsigned char> & sort, PhaseIO & b)
+{
+        if (sort.run()) return 1;
+        b.ids = sort.ids.Current();
+        return 0;
+}
+
+/* the pass that takes the rays as the call has them, in the arrays of the moment */
+template <int MODE, int FAST>
+static int launch_plain(struct tamd_view view, long n, bool again, const TraceRays & rays, int max_steps, int flags,
+    const PhaseIO & ph, ull * stats, ull * queue)
+{
+        return launch_trace<MODE, FAST != 0, false>(view, n, again, rays.pos, rays.dir, max_steps, rays.index,
+            rays.length, rays.n_steps, flags, ph, stats, counter_of(queue, TAMD_TRACE_QUEUE_A));
+}
+
+/* Phase A: the flat kernel where its rule holds (first_pass_flat: the closed-form pass of a fast,
+ * listed, uncapped first round), else the persistent one */
+template <int MODE>
+static int launch_phase_a(struct tamd_view view, long n, bool again, const TraceRays & rays, int max_steps, int flags,
+    const PhaseIO & a, const RayOut & out, ull * stats, ull * queue)
+{
+        if constexpr (MODE != TAMD_MODE_GENERIC) {
+                if (first_pass_flat(a.park_after, again, a.pg)) {
+                        const FirstPass fp = { a.park_after, a.mark_at, a.long_if, a.parked, a.n_parked,
+                                a.n_parked_back, a.sort_key, a.cross, a.pos_in, a.dir_in, a.index_in, a.dir_copy };
+                        return launch_first<MODE>(view, n, rays.pos, rays.dir, max_steps, rays.index, rays.length,
+                            rays.n_steps, flags, fp, out, stats);
+                }
+        }
+        return launch_plain<MODE, Fast::value>(view, n, again, rays, max_steps, flags, a, stats, queue);
+}
+
+/* Phase B: the rays on the hand-over list, each on its line; with `tail`, its idle waves locate
+ * the crossings of L1 (CrossTail) */
+template <int MODE>
+static int launch_lined(struct tamd_view view, long n, const TraceRays & rays, int max_steps, int flags,
+    const PhaseIO & b, const CrossTail & tail, ull * stats, ull * queue)
+{
+        const int tail_flag = (tail.words != nullptr) ? TRACE_CROSS_TAIL : 0;
+        return launch_trace<MODE, true, true>(view, n, true, rays.pos, rays.dir, max_steps, rays.index, rays.length,
+            rays.n_steps, flags | TRACE_CARRY_MEDIUM | tail_flag, b, stats, counter_of(queue, TAMD_TRACE_QUEUE_B));
 }
 
 /* One round of a trace: all the rays (pg.ids == NULL), or the ones the last
@@ -3675,164 +3825,74 @@ static char * sort_room_of(int * parked, long n)
  * threshold, a few to a wave on an otherwise empty chip, was wired in until round
  * 3 and always off: on C2 every threshold from 256 to 2 048 made the trace slower,
  * 6.9-7.8 ms against 6.0 ms.)
- * Without scratch for the lists (`parked` NULL: a batch beyond 2^31 rays) there
- * is one pass, which bisects in place. */
+ * Without scratch for the lists (`room` NULL: a batch beyond 2^31 rays, media that do not
+ * pack) there is one pass, which bisects in place. */
 template <int MODE>
-static int run_trace(struct tamd_view view, long n, double * pos, const double * dir,
-    int max_steps, int * index, double * length, int * n_steps, int flags, int * parked,
-    double * cross_ds, Paging pg, ull * stats, ull * queue)
+static int run_trace(struct tamd_view view, long n, TraceRays rays, int max_steps, int flags, char * room,
+    Paging pg, ull * stats, ull * queue)
 {
         const bool again = (pg.ids != nullptr);
-        const bool sort_room = (flags & TAMD_TRACE_SORT_ROOM) != 0;
-        flags &= ~TAMD_TRACE_SORT_ROOM;
         if (again) flags |= TRACE_CARRY_MEDIUM;
-        const int resume = again ? 2 : 0;
         const bool strict = g_math_strict || !view.fast_ok;
-        /* lists: parked[0 .. n) from A to B (from both ends), parked[n .. 3n) the crossings;
-         * counters, kQ words (a cache line or two) apart -- every wave of a pass adds to them:
-         * queue[0], [kQ]: the work queues of A, B; queue[2 kQ], [3 kQ]: the lengths of the lists;
-         * queue[4 kQ]: of the first list's far end; queue[5 kQ], [6 kQ], [7 kQ]: the lined pass's waves
-         * that know their queue dry, the tickets drawn on the crossings' list and the length of that
-         * list's far end (CrossTail) */
-        const bool listed = (parked != nullptr) && (cross_ds != nullptr) && (length != nullptr) &&
-            (n_steps != nullptr);
-        const CrossList none = { nullptr, nullptr, nullptr, nullptr };
-        const CrossList cross = { parked + n, cross_ds, queue + 3 * kQ, parked + 2 * n };
-        const PhaseIO one = { pg.ids, pg.n_in, nullptr, nullptr, 0, resume, pg, 0, 0, kChunk,
-                creep_lanes(n), dense_go(), listed ? cross : none };
-        /* the pass that takes the rays as the call has them (in the arrays of the moment: the
-         * spatial order below puts its own in their place) */
-        const auto first_pass = [&](auto fast, const PhaseIO & ph) {
-                return launch_trace<MODE, decltype(fast)::value, false>(view, n, again, pos, dir, max_steps, index,
-                    length, n_steps, flags, ph, stats, queue);
-        };
-        if (!listed) return with_math(strict, [&](auto fast) { return first_pass(fast, one); });
+        const bool listed = (room != nullptr) && (rays.length != nullptr) && (rays.n_steps != nullptr);
+        tamd_trace_room at;
+        tamd_trace_room_layout(&at, n);
+        CrossList cross = { nullptr, nullptr, nullptr, nullptr };
+        if (listed) {
+                cross.ray = TAMD_ROOM_AT(int, room, at.cross_ray), cross.ds = TAMD_ROOM_AT(double, room, at.cross_ds);
+                cross.count = counter_of(queue, TAMD_TRACE_N_CROSS);
+                cross.other = TAMD_ROOM_AT(int, room, at.cross_other);
+        }
+        PhaseIO shared = {}; /* (by every pass of the round) */
+        shared.pg = pg, shared.chunk = kChunk, shared.creep_lanes = creep_lanes(n), shared.dense_go = dense_go();
+        shared.cross = cross;
+        /* the only pass, where there is one: the rays as the call has them, to their end */
+        PhaseIO one = shared;
+        one.ids = pg.ids, one.n_dev = pg.n_in, one.accumulate = again ? 2 : 0;
+        if (!listed)
+                return with_math(strict, [&](auto fast) {
+                        return launch_plain<MODE, decltype(fast)::value>(view, n, again, rays, max_steps, flags, one,
+                            stats, queue);
+                });
         if (strict) {
-                if (first_pass(Strict(), one)) return 1;
-                return launch_cross<MODE, false>(view, n, pos, dir, index, length, n_steps, cross, pg, stats);
+                if (launch_plain<MODE, Strict::value>(view, n, again, rays, max_steps, flags, one, stats, queue)) return 1;
+                return launch_cross<MODE, false>(view, n, rays, cross, pg, stats);
         }
         const int park = park_threshold(MODE);
         if ((park <= 0) || (max_steps <= park)) {
-                if (first_pass(Fast(), one)) return 1;
-                return launch_cross<MODE, true>(view, n, pos, dir, index, length, n_steps, cross, pg, stats);
+                if (launch_plain<MODE, Fast::value>(view, n, again, rays, max_steps, flags, one, stats, queue)) return 1;
+                return launch_cross<MODE, true>(view, n, rays, cross, pg, stats);
         }
-        PhaseIO a = { pg.ids, pg.n_in, parked, queue + 2 * kQ, park, resume, pg, kDrainLanes, 0,
-                kChunk, creep_lanes(n), dense_go(), cross };
-        PhaseIO b = { parked, queue + 2 * kQ, nullptr, nullptr, 0, 1, pg, 0, park, kChunk,
-                creep_lanes(n), dense_go(), cross };
+        /* A: as `one`, up to `park` steps, then onto the hand-over list; B: from that list, lined */
+        PhaseIO a = one, b = shared;
+        a.parked = TAMD_ROOM_AT(int, room, at.parked), a.n_parked = counter_of(queue, TAMD_TRACE_N_PARKED);
+        a.park_after = park, a.drain_lanes = kDrainLanes;
+        b.ids = a.parked, b.n_dev = a.n_parked, b.accumulate = 1, b.line_after = park;
         b.pool = pool_on(MODE, n);
         /* (the lined pass's instances that have the code: fast, one map or one stack, nothing paged) */
         CrossTail tail = { nullptr };
         if ((MODE != TAMD_MODE_GENERIC) && (pg.faulted == nullptr) && cross_tail_on(n))
-                tail.words = queue + 1 * kQ + kQTail; /* (behind the lined pass's queue: see CrossTail) */
-        const int tail_flag = (tail.words != nullptr) ? TRACE_CROSS_TAIL : 0;
-        const int long_if = sort_long_if();
-        if (!again && (long_if > 0)) {
-                /* (a later round of a paged trace takes rays at any step count: unsorted) */
-                a.n_parked_back = queue + 4 * kQ, a.ds_mark = cross_ds + 2 * n, a.mark_at = park / 2;
-                a.long_if = (float)long_if;
-                b.n_dev_back = queue + 4 * kQ;
-        }
-        /* Room to ORDER the hand-over (internal.h, TAMD_TRACE_SORT_ROOM): keys beside the list, a
-         * radix sort (hipCUB) of the whole list's n places between the two passes -- places nobody
-         * filled carry a key (254) between the front's (0 .. 253) and the back's (255), so the front comes out first, in
-         * order, and the back stays at the far end, where the lined pass looks for it.  For batches
-         * small enough to be as long as their longest rays (sort_hand_over()). */
-        /* The rays in the order of where they start (k_ray_cells): keys and numbers into the sort's
-         * room, one pass of the radix sort.  The passes then WORK in that order -- a ray's state
-         * between the passes (position, medium, path length, step count, its direction) lives at its
-         * place in the ordered list, in arrays of the library's own -- while the caller's arrays are
-         * touched twice a ray: phase A reads a new ray from its place there, and whichever kernel
-         * ENDS a ray (k_cross for nearly all) writes its results to that place (RayOut); no pass of
-         * its own copies anything.  (Tried first: the passes working in the caller's arrays through
-         * the ordered list -- every hand-over then goes to a place of its own instead of next to
-         * its wave's: half the gain on C3, a loss on C4; and copies made by kernels of their own:
-         * 0.9 + 1.4 ms for C4's 12.5 M rays, more than the order gains there.)  Not over paged tiles
-         * (the pager's lists name rays by their place in the CALLER's arrays, round after round). */
+                tail.words = counter_of(queue, TAMD_TRACE_TAIL_N_DRY);
         RayOut out = { nullptr, nullptr, nullptr, nullptr, nullptr };
         if constexpr (MODE != TAMD_MODE_GENERIC) {
-                if (sort_room && !again && (pg.faulted == nullptr) && spatial_order(MODE, n)) {
-                        hipcub::DoubleBuffer<SPATIAL_KEY_T> cell((SPATIAL_KEY_T *)(parked + 5 * n),
-                            (SPATIAL_KEY_T *)(parked + 6 * n));
-                        hipcub::DoubleBuffer<int> list(parked, parked + 4 * n);
-                        size_t bytes = 0;
-                        if ((hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, cell, list, (int)n, 0, SPATIAL_BITS, g_stream) ==
-                                hipSuccess) &&
-                            (bytes <= TAMD_TRACE_SORT_TEMP)) {
-                                hipLaunchKernelGGL(k_ray_cells<MODE>, dim3(grid_for(n, 256)), dim3(256), 0, g_stream,
-                                    view, n, pos, cell.Current(), list.Current());
-                                LAUNCH_CHECK("k_ray_cells");
-                                char * const room = sort_room_of(parked, n);
-                                if (hipcub::DeviceRadixSort::SortPairs((void *)room, bytes, cell, list, (int)n, 0, SPATIAL_BITS,
-                                        g_stream) != hipSuccess)
-                                        return fail("hipcub::DeviceRadixSort", hipGetLastError());
-                                /* the arrays the passes work in, and the list, which must outlive them
-                                 * (they use parked[0, n) and the sort's room again): 72 bytes a ray */
-                                char * copies = room + TAMD_TRACE_SORT_TEMP;
-                                double * const pos_s = (double *)copies;
-                                double * const dir_s = pos_s + 3 * n;
-                                double * const length_s = dir_s + 3 * n;
-                                int * const index_s = (int *)(length_s + n);
-                                int * const n_steps_s = index_s + 2 * n;
-                                int * const kept = n_steps_s + n;
-                                HIP_TRY(hipMemcpyAsync(kept, list.Current(), (size_t)n * sizeof(int),
-                                    hipMemcpyDeviceToDevice, g_stream));
-                                out.order_of = kept, out.pos = pos, out.index = index, out.length = length,
-                                out.n_steps = n_steps;
-                                a.out = out, b.out = out;
-                                a.pos_in = pos, a.dir_in = dir, a.index_in = index, a.dir_copy = dir_s;
-                                pos = pos_s, dir = dir_s, index = index_s, length = length_s, n_steps = n_steps_s;
-                        }
-                }
+                if (!again && (pg.faulted == nullptr) && spatial_order(MODE, n))
+                        if (order_rays<MODE>(view, n, room, at, rays, a, b, out)) return 1;
         }
-        const bool order = sort_room && !again && (a.n_parked_back != nullptr) && sort_hand_over(n);
-        hipcub::DoubleBuffer<unsigned char> keys((unsigned char *)(parked + 5 * n), (unsigned char *)(parked + 6 * n));
-        hipcub::DoubleBuffer<int> ids(parked, parked + 4 * n);
-        void * const sort_temp = (void *)sort_room_of(parked, n);
-        size_t temp_bytes = 0;
+        RoomSort<unsigned char> hand_over(room, at, n, 8);
         bool sorting = false;
-        if (order) {
-                if ((hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys, ids, (int)n, 0, 8, g_stream) ==
-                        hipSuccess) &&
-                    (temp_bytes <= TAMD_TRACE_SORT_TEMP)) {
-                        sorting = true;
-                        a.sort_key = keys.Current();
-                        HIP_TRY(hipMemsetAsync(keys.Current(), 0xFE, (size_t)n, g_stream));
-                }
-        }
-        bool flat = false;
-        if constexpr (MODE != TAMD_MODE_GENERIC) {
-                if (first_pass_flat(park, again, pg)) {
-                        /* (the closed-form pass of a fast, listed, uncapped first round: k_first) */
-                        flat = true;
-                        const FirstPass fp = { park, a.mark_at, a.long_if, parked, a.n_parked, a.n_parked_back,
-                                a.sort_key, cross, a.pos_in, a.dir_in, a.index_in, a.dir_copy };
-                        if (launch_first<MODE>(view, n, pos, dir, max_steps, index, length, n_steps, flags, fp, out,
-                                stats))
-                                return 1;
-                }
-        }
-        if (!flat && first_pass(Fast(), a)) return 1;
-        if (sorting) {
-                if (hipcub::DeviceRadixSort::SortPairs(sort_temp, temp_bytes, keys, ids, (int)n, 0, 8, g_stream) !=
-                    hipSuccess)
-                        return fail("hipcub::DeviceRadixSort", hipGetLastError());
-                b.ids = ids.Current();
-        }
-        if (launch_trace<MODE, true, true>(view, n, true, pos, dir, max_steps, index, length,
-                n_steps, flags | TRACE_CARRY_MEDIUM | tail_flag, b, stats, queue + 1 * kQ))
-                return 1;
-        return launch_cross<MODE, true>(view, n, pos, dir, index, length, n_steps, cross, pg, stats, out, tail);
+        if (hand_over_plan(hand_over, n, again, queue, TAMD_ROOM_AT(double, room, at.ds_mark), a, b, sorting)) return 1;
+        if (launch_phase_a<MODE>(view, n, again, rays, max_steps, flags, a, out, stats, queue)) return 1;
+        if (sorting && hand_over_sort(hand_over, b)) return 1;
+        if (launch_lined<MODE>(view, n, rays, max_steps, flags, b, tail, stats, queue)) return 1;
+        return launch_cross<MODE, true>(view, n, rays, cross, pg, stats, out, tail);
 }
 
-/* queue: eight counters (see run_trace); parked: room for 3 n ray ids and cross_ds
- * for 3 n doubles (the lists of the passes; what the hand-over sorts by in the last n),
- * or NULL.  pg: the round of a paged
- * geometry (paging.c), all NULL otherwise; the counters in `stats` add up over the
- * rounds of a call. */
+/* room: the stepper's scratch laid out for n rays (trace_room.h), or NULL.  pg: the round of a
+ * paged geometry (paging.c), all NULL otherwise; the counters in `stats` add up over the rounds
+ * of a call. */
 extern "C" int tamd_k_trace(struct tamd_view view, long n, double * pos,
     const double * dir, int max_steps, int * index, double * length, int * n_steps,
-    int flags, int * parked, double * cross_ds, struct tamd_paging pg, unsigned long long * stats,
+    int flags, void * room, struct tamd_paging pg, unsigned long long * stats,
     unsigned long long * queue)
 {
         if (tamd_dev_init()) return 1;
@@ -3846,13 +3906,12 @@ extern "C" int tamd_k_trace(struct tamd_view view, long n, double * pos,
                 return 1;
         }
         if (pg.ids == nullptr) HIP_TRY(hipMemsetAsync(stats, 0, 4 * sizeof(ull), g_stream));
-        HIP_TRY(hipMemsetAsync(queue, 0, 8 * kQ * sizeof(ull), g_stream));
+        HIP_TRY(hipMemsetAsync(queue, 0, TAMD_TRACE_COUNTERS * sizeof(ull), g_stream));
         if (n <= 0) return 0;
-        const int carry = ((flags & TURTLE_AMD_TRACE_RESUME) ? TRACE_CARRY_MEDIUM : 0) |
-            ((parked != nullptr) ? (flags & TAMD_TRACE_SORT_ROOM) : 0);
+        const int carry = (flags & TURTLE_AMD_TRACE_RESUME) ? TRACE_CARRY_MEDIUM : 0;
+        const TraceRays rays = { pos, dir, index, length, n_steps };
         return with_mode(view.mode, [&](auto mode) {
-                return run_trace<decltype(mode)::value>(view, n, pos, dir, max_steps, index, length,
-                    n_steps, carry, parked, cross_ds, pg, stats, queue);
+                return run_trace<decltype(mode)::value>(view, n, rays, max_steps, carry, (char *)room, pg, stats, queue);
         });
 }
 

@@ -273,10 +273,9 @@ struct turtle_stepper {
         size_t d_tables_size;
         struct tamd_view view;
         int n_table;                  /* entries of the tile table (all stacks) */
-        unsigned long long * d_stats; /* 4 stats + the TAMD_TRACE_COUNTERS of a trace */
-        int * d_parked;               /* scratch of the batch calls: ray ids ... */
-        double * d_scratch_ds;        /* ... and one double each (same block) */
-        long parked_capacity;
+        unsigned long long * d_stats; /* TAMD_STATS_WORDS words (internal.h) */
+        void * d_room;                /* scratch of the batch calls, laid out by trace_room.h ... */
+        long room_capacity;           /* ... for up to this many rays (< 0 after a device failure) */
         int last_rounds;              /* rounds the last batch call took (1: nothing was paged in) */
         int view_out;                 /* a device view of it is out (turtle_amd_stepper_view_acquire): its
                                        * tables stay as they are until the release */

@@ -134,30 +134,43 @@ int tamd_k_clearance(struct tamd_view view, int n_items, int n_targets, int pair
 int tamd_k_step(struct tamd_view view, long n, double * pos,
     const double * dir, double * lat, double * lon, double * alt,
     double * elev, double * step, int * index, int flags, struct tamd_paging pg);
-/* stats: 4 x uint64 on the device (rays, steps, samples, capped); queue:
- * TAMD_TRACE_COUNTERS x uint64 (work queues and list lengths of the passes of a
- * fast trace: see run_trace in device.hip); both zeroed by the launcher.
- * parked: int[3 n] and cross_ds: double[n], scratch for the lists of rays handed
- * from pass to pass (the long rays; the rays that crossed a boundary, for
- * k_cross), or NULL for a single-pass launch that bisects in place; with them,
- * length and n_steps must not be NULL.  With TAMD_TRACE_SORT_ROOM in `flags`,
- * `parked` has room for TAMD_TRACE_SORT_INTS x n ints and TAMD_TRACE_SORT_TEMP
- * bytes more behind them: the hand-over list is then ORDERED before the lined
- * pass reads it (run_trace in device.hip). */
-#define TAMD_TRACE_COUNTERS 128
-#define TAMD_TRACE_SORT_ROOM 0x100
+/* The counters of a trace's passes, in the `queue` of tamd_k_trace: counter c is the word
+ * queue[c * TAMD_TRACE_COUNTER_STRIDE] -- a cache line or two apart, every wave of a pass adds to
+ * them.  The lined pass's kernel is given B's queue and finds the tail's three behind it
+ * (device.hip, CrossTail): their order and distance from TAMD_TRACE_QUEUE_B are part of it. */
+enum tamd_trace_counter {
+        TAMD_TRACE_QUEUE_A = 0,     /* the work queue of the first pass (phase A; or the only pass) */
+        TAMD_TRACE_QUEUE_B,         /* ... of the lined pass */
+        TAMD_TRACE_N_PARKED,        /* the length of the hand-over list (from its front) */
+        TAMD_TRACE_N_CROSS,         /* the length of the crossings' list (L1, from its front) */
+        TAMD_TRACE_N_PARKED_BACK,   /* the length of the hand-over list's far end */
+        TAMD_TRACE_TAIL_N_DRY,      /* CrossTail: the lined pass's waves that know their queue dry */
+        TAMD_TRACE_TAIL_L1_NEXT,    /* ... the tickets drawn on the crossings' list */
+        TAMD_TRACE_TAIL_L2_COUNT,   /* ... the length of that list's far end (L2) */
+        TAMD_TRACE_N_COUNTERS
+};
+#define TAMD_TRACE_COUNTER_STRIDE 16
+#define TAMD_TRACE_COUNTERS (TAMD_TRACE_N_COUNTERS * TAMD_TRACE_COUNTER_STRIDE)
+/* A stepper's words on the device (host.h: d_stats): the 4 stats of its last batch call, the
+ * `queue` of the launchers (a trace's counters; the others use its first three words), and the
+ * step kernels' own stats of a paged traverse, which keeps its sums in the first 4 meanwhile. */
+#define TAMD_STATS_QUEUE 4
+#define TAMD_STATS_STEPS (TAMD_STATS_QUEUE + TAMD_TRACE_COUNTERS)
+#define TAMD_STATS_WORDS (TAMD_STATS_STEPS + 4)
+/* stats: 4 x uint64 on the device (rays, steps, samples, capped); queue: TAMD_TRACE_COUNTERS x
+ * uint64 (enum tamd_trace_counter); both zeroed by the launcher.
+ * room: the stepper's scratch block, laid out for THIS n by tamd_trace_room_layout() (trace_room.h: the
+ * lists of rays handed from pass to pass, the sorts' room, the ordered copies), or NULL for a
+ * single-pass launch that bisects in place; with it, length and n_steps must not be NULL.  (The
+ * caller gives NULL too where the lists cannot be used: media that do not pack into 16 bits.)
+ * pg.tentative is the caller's to set, from the same layout. */
+int tamd_k_trace(struct tamd_view view, long n, double * pos,
+    const double * dir, int max_steps, int * index, double * length,
+    int * n_steps, int flags, void * room, struct tamd_paging pg,
+    unsigned long long * stats, unsigned long long * queue);
 /* a flag of the step kernels beside enum turtle_amd_step_flags: `alt` holds the tentative length
  * of the next step instead of the altitude, `elev` is not used (turtle_stepper_walk_n) */
 #define TAMD_STEP_COMPACT 0x200
-#define TAMD_TRACE_SORT_INTS 7
-#define TAMD_TRACE_SORT_TEMP ((size_t)32 << 20)
-/* ... and, behind those, TAMD_TRACE_COPY_BYTES x n bytes for the rays themselves in the order
- * the trace takes them (position, direction, index, path length, step count) */
-#define TAMD_TRACE_COPY_BYTES 72
-int tamd_k_trace(struct tamd_view view, long n, double * pos,
-    const double * dir, int max_steps, int * index, double * length,
-    int * n_steps, int flags, int * parked, double * cross_ds, struct tamd_paging pg,
-    unsigned long long * stats, unsigned long long * queue);
 /* n single steps with a direction: the step kernel lists the rays that crossed
  * a boundary (cross_ray / cross_ds: scratch for n entries each, or NULL to
  * bisect in place) and a second kernel bisects them, packed; `flags` are enum

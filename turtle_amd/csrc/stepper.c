@@ -9,6 +9,7 @@
  * of device.hip.  Scalar entry points are the batch ones with n = 1.
  */
 #include "host.h"
+#include "trace_room.h"
 
 #include <time.h>
 
@@ -29,15 +30,15 @@
 static void stepper_release_device(struct turtle_stepper * s)
 {
         int drained = 1;
-        if ((s->d_tables != NULL) || (s->d_stats != NULL) || (s->d_parked != NULL))
+        if ((s->d_tables != NULL) || (s->d_stats != NULL) || (s->d_room != NULL))
                 drained = (tamd_dev_sync_device(s->device) == 0);
         if (drained) { /* else: leaked, rather than freed under a launch that may still read it */
                 tamd_dev_free_on(s->device, s->d_tables);
                 tamd_dev_free_on(s->device, s->d_stats);
-                tamd_dev_free_on(s->device, s->d_parked);
+                tamd_dev_free_on(s->device, s->d_room);
         }
-        s->d_tables = NULL, s->d_stats = NULL, s->d_parked = NULL, s->d_scratch_ds = NULL;
-        s->d_tables_size = 0, s->parked_capacity = 0, s->epoch = 0;
+        s->d_tables = NULL, s->d_stats = NULL, s->d_room = NULL;
+        s->d_tables_size = 0, s->room_capacity = 0, s->epoch = 0;
 }
 
 /* The stepper's HBM (tables, counters, scratch) is on the device of the thread
@@ -328,7 +329,7 @@ int tamd_stepper_flatten(struct turtle_stepper * s, char * message, size_t size)
 {
         if (stepper_bind_device(s)) return -1;
         if (s->d_stats == NULL) {
-                const size_t words = 4 + TAMD_TRACE_COUNTERS;
+                const size_t words = TAMD_STATS_WORDS;
                 if (tamd_dev_malloc((void **)&s->d_stats, words * sizeof(*s->d_stats))) return -1;
                 if (tamd_dev_zero(s->d_stats, words * sizeof(*s->d_stats))) return -1;
         }
@@ -982,40 +983,40 @@ enum turtle_return turtle_stepper_clearance_n(struct turtle_stepper * stepper, l
         return sight_run(&error_, l, stepper, space, &clearance_resident, &a);
 }
 
-/* Grow-only scratch of the batch calls: 4 n ints (the rays a trace hands from
- * pass to pass, the rays whose step crossed a boundary and what they found
- * there / the rays a batch of steps defers to its bisection pass; the step
- * counts of a trace whose caller wants none) followed by 4 n doubles (the step a
- * ray that waits for a tile was about to take; the crossing steps; the path
- * lengths of a trace whose caller wants none; the step lengths a trace sorts its
- * hand-over by).  0 if it holds n entries; 1 if n
- * is beyond an int (the caller does without); parked_capacity < 0 after a device
+/* Grow-only scratch of the batch calls: one block, whose regions trace_room.h names and lays
+ * out for the n of each call (a block for more rays holds every smaller layout).  0 if it holds
+ * n rays; 1 if n is beyond an int (the caller does without); room_capacity < 0 after a device
  * failure. */
 static int tamd_stepper_scratch(struct turtle_stepper * stepper, long n)
 {
         if (n >= 2147483647L) return 1;
         if (stepper_bind_device(stepper)) {
-                stepper->parked_capacity = -1;
+                stepper->room_capacity = -1;
                 return 1;
         }
-        if (n <= stepper->parked_capacity) return 0;
-        if (stepper->d_parked != NULL) {
+        if (n <= stepper->room_capacity) return 0;
+        if (stepper->d_room != NULL) {
                 tamd_dev_sync();
-                tamd_dev_free(stepper->d_parked);
-                stepper->d_parked = NULL;
+                tamd_dev_free(stepper->d_room);
+                stepper->d_room = NULL;
         }
-        /* (the lists of the passes, and room to order the hand-over: internal.h) */
-        /* (+ 256: the sort's room begins at the next multiple of 256 bytes behind the ints) */
-        const size_t ints = ((((size_t)n * TAMD_TRACE_SORT_INTS * sizeof(int) + 256 + TAMD_TRACE_SORT_TEMP +
-                                  (size_t)n * TAMD_TRACE_COPY_BYTES) + 255) / 256) * 256;
-        stepper->parked_capacity = 0;
-        if (tamd_dev_malloc((void **)&stepper->d_parked, ints + (size_t)n * 4 * sizeof(double))) {
-                stepper->parked_capacity = -1;
+        struct tamd_trace_room room;
+        stepper->room_capacity = 0;
+        if (tamd_dev_malloc(&stepper->d_room, tamd_trace_room_layout(&room, n))) {
+                stepper->room_capacity = -1;
                 return 1;
         }
-        stepper->d_scratch_ds = (double *)((char *)stepper->d_parked + ints);
-        stepper->parked_capacity = n;
+        stepper->room_capacity = n;
         return 0;
+}
+
+/* the crossing list of a batch of n single steps, in the scratch (n rays fit: the caller saw to it) */
+static int * stepper_cross_list(const struct turtle_stepper * stepper, long n, double ** cross_ds)
+{
+        struct tamd_trace_room room;
+        tamd_trace_room_layout(&room, n);
+        *cross_ds = TAMD_ROOM_AT(double, stepper->d_room, room.cross_ds);
+        return TAMD_ROOM_AT(int, stepper->d_room, room.cross_ray);
 }
 
 struct step_args {
@@ -1031,9 +1032,11 @@ static int step_round(struct turtle_stepper * stepper, struct tamd_paging pg, in
         if (a->dir == NULL)
                 return tamd_k_step(stepper->view, a->n, a->pos, a->dir, a->lat, a->lon, a->alt,
                     a->elev, a->step, a->index, a->flags, pg);
+        double * cross_ds = NULL;
+        int * const cross_ray = a->listed ? stepper_cross_list(stepper, a->n, &cross_ds) : NULL;
         return tamd_k_step_dir(stepper->view, a->n, a->pos, a->dir, a->lat, a->lon, a->alt, a->elev,
-            a->step, a->index, a->flags, a->listed ? stepper->d_parked : NULL,
-            a->listed ? stepper->d_scratch_ds : NULL, pg, stepper->d_stats, stepper->d_stats + 4);
+            a->step, a->index, a->flags, cross_ray, cross_ds, pg, stepper->d_stats,
+            stepper->d_stats + TAMD_STATS_QUEUE);
 }
 
 static enum turtle_return step_n(struct tamd_error * error, struct turtle_stepper * stepper,
@@ -1066,7 +1069,7 @@ static enum turtle_return step_n(struct tamd_error * error, struct turtle_steppe
         /* with a direction: two passes, the second for the rays that crossed a
          * boundary (a single step bisects in place: nothing to pack) */
         args.listed = (direction != NULL) && (n > 1) && (tamd_stepper_scratch(stepper, n) == 0);
-        if ((direction != NULL) && (n > 1) && !args.listed && (stepper->parked_capacity < 0))
+        if ((direction != NULL) && (n > 1) && !args.listed && (stepper->room_capacity < 0))
                 return TAMD_RAISE_DEVICE();
         const int rc = stepper_rounds(stepper, n, &step_round, &args);
         if (rc != 0) return RAISE_ROUNDS(stepper, rc);
@@ -1088,9 +1091,11 @@ static int walk_round(struct turtle_stepper * stepper, struct tamd_paging pg, in
 {
         struct walk_args * a = p;
         (void)round;
+        double * cross_ds;
+        int * const cross_ray = stepper_cross_list(stepper, a->n, &cross_ds);
         return tamd_k_step_walk(stepper->view, a->n, a->pos, a->alt, a->elev, a->index, a->seed,
-            a->stream, a->first, a->length, a->steps, stepper->d_parked, stepper->d_scratch_ds, pg,
-            stepper->d_stats, stepper->d_stats + 4);
+            a->stream, a->first, a->length, a->steps, cross_ray, cross_ds, pg, stepper->d_stats,
+            stepper->d_stats + TAMD_STATS_QUEUE);
 }
 
 static int walk_start_round(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
@@ -1106,7 +1111,8 @@ static int walk_resident(struct turtle_stepper * stepper, struct tamd_paging pg,
         struct walk_args * a = p;
         (void)pg, (void)round;
         return tamd_k_walk(stepper->view, a->n, a->pos, a->alt, a->elev, a->index, a->seed, a->first,
-            a->first_step, a->n_steps, a->length, a->steps, stepper->d_stats, stepper->d_stats + 4);
+            a->first_step, a->n_steps, a->length, a->steps, stepper->d_stats,
+            stepper->d_stats + TAMD_STATS_QUEUE);
 }
 
 enum turtle_return turtle_stepper_scatter_n(struct turtle_stepper * stepper, long n,
@@ -1122,7 +1128,7 @@ enum turtle_return turtle_stepper_scatter_n(struct turtle_stepper * stepper, lon
                 return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid input parameter(s)");
         if (n <= 0) return TURTLE_RETURN_SUCCESS;
         if (tamd_stepper_scratch(stepper, n) != 0) {
-                if (stepper->parked_capacity < 0) return TAMD_RAISE_DEVICE();
+                if (stepper->room_capacity < 0) return TAMD_RAISE_DEVICE();
                 return TAMD_RAISE(TURTLE_RETURN_MEMORY_ERROR, "batch too large");
         }
         struct tamd_stage st = { 0 };
@@ -1200,12 +1206,14 @@ static int trace_round(struct turtle_stepper * stepper, struct tamd_paging pg, i
 {
         struct trace_args * a = p;
         (void)round;
-        pg.tentative = a->scratch ? stepper->d_scratch_ds : NULL;
+        struct tamd_trace_room room;
+        tamd_trace_room_layout(&room, a->n);
+        pg.tentative = a->scratch ? TAMD_ROOM_AT(double, stepper->d_room, room.tentative) : NULL;
         /* the lists of the passes; the packed media of the crossings hold 16 bits each */
         const int listed = a->scratch && (stepper->n_layers < 65000) && (stepper->n_data < 65000);
         return tamd_k_trace(stepper->view, a->n, a->pos, a->dir, a->max_steps, a->index, a->length,
-            a->n_steps, a->flags | (listed ? TAMD_TRACE_SORT_ROOM : 0), listed ? stepper->d_parked : NULL,
-            listed ? stepper->d_scratch_ds + a->n : NULL, pg, stepper->d_stats, stepper->d_stats + 4);
+            a->n_steps, a->flags, listed ? stepper->d_room : NULL, pg, stepper->d_stats,
+            stepper->d_stats + TAMD_STATS_QUEUE);
 }
 
 enum turtle_return turtle_stepper_trace_n(struct turtle_stepper * stepper, long n,
@@ -1217,7 +1225,7 @@ enum turtle_return turtle_stepper_trace_n(struct turtle_stepper * stepper, long 
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
         struct trace_args args = { n, NULL, NULL, NULL, NULL, NULL, max_steps, flags, 0 };
         args.scratch = (tamd_stepper_scratch(stepper, n) == 0);
-        if (!args.scratch && (stepper->parked_capacity < 0)) return TAMD_RAISE_DEVICE();
+        if (!args.scratch && (stepper->room_capacity < 0)) return TAMD_RAISE_DEVICE();
         struct tamd_stage st = { 0 };
         const size_t nb = (size_t)n * sizeof(double);
         tamd_stage_add(&st, position, 3 * nb, TAMD_INOUT, &args.pos);
@@ -1235,8 +1243,10 @@ enum turtle_return turtle_stepper_trace_n(struct turtle_stepper * stepper, long 
                 return TAMD_RAISE(TURTLE_RETURN_MEMORY_ERROR,
                     "a batch this large cannot run over stacks with tiles left to page in");
         if (args.scratch && (n > 0)) { /* (in place of the NULL of an array that is not brought back) */
-                if (args.length == NULL) args.length = stepper->d_scratch_ds + 2 * n;
-                if (args.n_steps == NULL) args.n_steps = stepper->d_parked + 3 * n;
+                struct tamd_trace_room room;
+                tamd_trace_room_layout(&room, n);
+                if (args.length == NULL) args.length = TAMD_ROOM_AT(double, stepper->d_room, room.own_length);
+                if (args.n_steps == NULL) args.n_steps = TAMD_ROOM_AT(int, stepper->d_room, room.own_n_steps);
         }
         const int rc = stepper_rounds(stepper, n, &trace_round, &args);
         if (rc != 0) return RAISE_ROUNDS(stepper, rc);
@@ -1265,8 +1275,10 @@ static int traverse_round(struct turtle_stepper * stepper, struct tamd_paging pg
 {
         struct traverse_args * a = p;
         (void)round;
+        double * cross_ds;
+        int * const cross_ray = stepper_cross_list(stepper, a->n, &cross_ds);
         return tamd_k_step_live(stepper->view, a->n, a->pos, a->dir, a->alt, a->elev, a->step, a->live,
-            stepper->d_parked, stepper->d_scratch_ds, pg, stepper->d_stats + 4 + 4, stepper->d_stats + 4);
+            cross_ray, cross_ds, pg, stepper->d_stats + TAMD_STATS_STEPS, stepper->d_stats + TAMD_STATS_QUEUE);
 }
 
 static void * traverse_piece(char * block, size_t * used, size_t bytes)
@@ -1301,11 +1313,11 @@ static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos,
         double * total = (rec != NULL) ? traverse_piece(block, &used, nb) : NULL;
         if (n_steps == NULL) n_steps = own;
         if (n_cross == NULL) n_cross = own + n;
-        /* counters: [0, 4) k_traverse_gen's; the step kernels' stats are in d_stats[8, 12) */
+        /* counters: [0, 4) k_traverse_gen's; the step kernels' stats are at d_stats + TAMD_STATS_STEPS */
         int rc = stepper_rounds(stepper, n, &traverse_start_round, &a);
         int rounds = stepper->last_rounds; /* (turtle_amd_stepper_rounds: the most a generation took) */
         if ((rc == 0) && (tamd_dev_zero(counters, 4 * sizeof(*counters)) ||
-                             tamd_dev_zero(stepper->d_stats + 8, 4 * sizeof(*stepper->d_stats)) ||
+                             tamd_dev_zero(stepper->d_stats + TAMD_STATS_STEPS, 4 * sizeof(*stepper->d_stats)) ||
                              ((total != NULL) && tamd_dev_zero(total, nb)) ||
                              tamd_k_traverse_gen(n, 1, a.alt, NULL, a.live, medium, index, length,
                                  n_steps, n_cross, ceiling, max_steps, counters)))
@@ -1333,7 +1345,8 @@ static int traverse_paged(struct turtle_stepper * stepper, long n, double * pos,
         /* turtle_stepper_trace_stats: rays, steps, samples (the origins' and the step kernels'),
          * rays stopped by max_steps */
         unsigned long long taken[4];
-        if ((rc == 0) && tamd_dev_d2h(taken, stepper->d_stats + 8, sizeof(taken))) rc = TURTLE_RETURN_LIBRARY_ERROR;
+        if ((rc == 0) && tamd_dev_d2h(taken, stepper->d_stats + TAMD_STATS_STEPS, sizeof(taken)))
+                rc = TURTLE_RETURN_LIBRARY_ERROR;
         if (rc == 0) {
                 const unsigned long long stats[4] = { c[0], c[1], (unsigned long long)n + taken[2], c[2] };
                 if (tamd_dev_h2d(stepper->d_stats, stats, sizeof(stats))) rc = TURTLE_RETURN_LIBRARY_ERROR;
@@ -1357,7 +1370,7 @@ static int sight_resident(struct turtle_stepper * stepper, struct tamd_paging pg
         struct sight_args * a = p;
         (void)pg, (void)round;
         return tamd_k_traverse(stepper->view, a->n, a->pos, a->dir, a->ceiling, a->max_steps, a->index,
-            a->length, a->n_steps, a->n_cross, a->rec, stepper->d_stats, stepper->d_stats + 4);
+            a->length, a->n_steps, a->n_cross, a->rec, stepper->d_stats, stepper->d_stats + TAMD_STATS_QUEUE);
 }
 
 /* turtle_stepper_traverse_n and, rec != NULL (the caller's arrays), turtle_stepper_crossings_n */
@@ -1374,7 +1387,7 @@ static enum turtle_return traverse_n(struct tamd_error * error, struct turtle_st
         if (rc != 0) return RAISE_ROUNDS(stepper, rc);
         const int paged = stepper_is_paged(stepper);
         if (paged && (tamd_stepper_scratch(stepper, n) != 0)) {
-                if (stepper->parked_capacity < 0) return TAMD_RAISE_DEVICE();
+                if (stepper->room_capacity < 0) return TAMD_RAISE_DEVICE();
                 return TAMD_RAISE(TURTLE_RETURN_MEMORY_ERROR, "batch too large");
         }
         const long media = stepper->n_layers + 1;
