@@ -1822,6 +1822,49 @@ __device__ __forceinline__ int normal(const Geometry<MODE, MATH> & g, const doub
         return found;
 }
 
+/* ---- the step machine of Stepping::trip() below and of the library's k_walk ----
+ * One sample per live lane and trip, at q = B + d * t: the origin itself (ST_INIT, the callers'
+ * own business), a tentative step (ST_STEP: t = ds), or one halving of a crossing (ST_BISECT:
+ * t = (ds0 + ds1) / 2 about B, the tentative position that crossed).  (k_traverse keeps a copy
+ * of its own, for the reason of speed given there.) */
+enum { ST_INIT = 0, ST_STEP = 1, ST_BISECT = 2 };
+
+/* What a ray keeps while a crossing is located: the bracket, and the halving's last sample of the
+ * other medium, which the ray goes on from [ref stepper.c:849-858]. */
+struct Bisection {
+        double ds0, ds1;
+        double b_alt, b_e0, b_e1;
+        int bm, bk, halvings;
+};
+struct StepOutcome {
+        bool accept;  /* a ST_STEP sample in the ray's medium: the step stands, B is its end */
+        bool located; /* the bracket is closed: the crossing is at B + d * ds1 [ref stepper.c:861-863] */
+};
+
+/* The bookkeeping of one sample `s` of a ray in medium m whose tentative step is ds, as selects.
+ * A ST_STEP sample moves B to q; one of another medium opens or narrows the bracket (1e-8 m, or
+ * 1200 halvings: the guard).  What an accepted step and a located crossing mean to the ray is the
+ * caller's, who sets the state back to ST_STEP after a located crossing. */
+__device__ __forceinline__ StepOutcome step_or_bisect(Bisection & b, int & state, double & bx, double & by,
+    double & bz, int m, double ds, double t, double qx, double qy, double qz, const Sample & s)
+{
+        const bool stepping = (state == ST_STEP);
+        const bool same = (s.m == m);
+        const bool accept = stepping & same;
+        const bool cross = stepping & !same;
+        const bool other = !same;
+        bx = stepping ? qx : bx, by = stepping ? qy : by, bz = stepping ? qz : bz;
+        b.bm = other ? s.m : b.bm, b.bk = other ? s.k : b.bk;
+        b.b_alt = other ? s.alt : b.b_alt, b.b_e0 = other ? s.e0 : b.b_e0, b.b_e1 = other ? s.e1 : b.b_e1;
+        b.ds0 = cross ? -ds : ((!stepping & same) ? t : b.ds0);
+        b.ds1 = cross ? 0. : ((!stepping & other) ? t : b.ds1);
+        b.halvings = stepping ? 0 : b.halvings + 1;
+        state = cross ? ST_BISECT : state;
+        const bool located = (state == ST_BISECT) & !cross &
+            (!(b.ds1 - b.ds0 > 1E-08) | (b.halvings > 1200));
+        return { accept, located };
+}
+
 /* what a trip() reports */
 enum Event {
         NONE = 0,     /* nothing yet: the ray is halving a crossing, or is not live */
@@ -1854,7 +1897,7 @@ struct Stepping {
         int from;            /* of the last event: the medium left */
         bool live;
 
-        __device__ __forceinline__ Stepping() : live(false), state_(ST_ORIGIN_) {}
+        __device__ __forceinline__ Stepping() : live(false), state_(ST_INIT) {}
 
         /* a new ray: the next trip() samples its origin */
         __device__ __forceinline__ void start(const double pos[3], const double dir[3])
@@ -1862,7 +1905,7 @@ struct Stepping {
                 x[0] = pos[0], x[1] = pos[1], x[2] = pos[2];
                 d[0] = dir[0], d[1] = dir[1], d[2] = dir[2];
                 index[0] = index[1] = -1, length = 0., from = -1;
-                state_ = ST_ORIGIN_, live = true;
+                state_ = ST_INIT, live = true;
         }
 
         /* a ray whose sample is known (of sample(), step(), a batch call): the next trip() steps */
@@ -1873,7 +1916,7 @@ struct Stepping {
                 d[0] = dir[0], d[1] = dir[1], d[2] = dir[2];
                 altitude = alt, elevation[0] = e0, elevation[1] = e1, index[0] = medium, index[1] = data;
                 length = 0., from = -1;
-                state_ = ST_STEP_, live = (medium >= 0);
+                state_ = ST_STEP, live = (medium >= 0);
                 ds_ = d_step_length(g.v, alt, e0, e1, medium);
         }
 
@@ -1888,9 +1931,9 @@ struct Stepping {
                 int event = NONE;
                 if (live) {
                         /* ---- one sample at q = B + d * t (the origin itself first) ---- */
-                        const bool init = (state_ == ST_ORIGIN_);
-                        const bool stepping = (state_ == ST_STEP_);
-                        const double t = stepping ? ds_ : 0.5 * (ds0_ + ds1_);
+                        const bool init = (state_ == ST_INIT);
+                        const bool stepping = (state_ == ST_STEP);
+                        const double t = stepping ? ds_ : 0.5 * (b_.ds0 + b_.ds1);
                         const double qx = init ? x[0] : x[0] + d[0] * t, qy = init ? x[1] : x[1] + d[1] * t,
                                      qz = init ? x[2] : x[2] + d[2] * t;
                         Sample s;
@@ -1898,34 +1941,21 @@ struct Stepping {
                         if (init) { /* [ref stepper.c:780-796] */
                                 index[0] = s.m, index[1] = s.k;
                                 altitude = s.alt, elevation[0] = s.e0, elevation[1] = s.e1;
-                                state_ = ST_STEP_;
+                                state_ = ST_STEP;
                                 event = ORIGIN;
                         } else {
-                                /* ---- bookkeeping: stepping and halving together, as selects ---- */
-                                const bool same = (s.m == index[0]);
-                                const bool accept = stepping & same;
-                                const bool cross = stepping & !same;
-                                const bool other = !same;
-                                x[0] = stepping ? qx : x[0], x[1] = stepping ? qy : x[1], x[2] = stepping ? qz : x[2];
-                                bm_ = other ? s.m : bm_, bk_ = other ? s.k : bk_;
-                                b_alt_ = other ? s.alt : b_alt_, b_e0_ = other ? s.e0 : b_e0_, b_e1_ = other ? s.e1 : b_e1_;
-                                ds0_ = cross ? -ds_ : ((!stepping & same) ? t : ds0_);
-                                ds1_ = cross ? 0. : ((!stepping & other) ? t : ds1_);
-                                halvings_ = stepping ? 0 : halvings_ + 1;
-                                state_ = cross ? ST_HALVE_ : state_;
-                                const bool located = (state_ == ST_HALVE_) & !cross &
-                                    (!(ds1_ - ds0_ > 1E-08) | (halvings_ > 1200));
-                                if (accept) {
+                                const StepOutcome o = step_or_bisect(b_, state_, x[0], x[1], x[2], index[0], ds_, t, qx, qy, qz, s);
+                                if (o.accept) {
                                         length = ds_, from = index[0], index[1] = s.k;
                                         altitude = s.alt, elevation[0] = s.e0, elevation[1] = s.e1;
                                         event = STEP;
                                 }
-                                if (located) { /* [ref stepper.c:861-863] */
-                                        x[0] = x[0] + d[0] * ds1_, x[1] = x[1] + d[1] * ds1_, x[2] = x[2] + d[2] * ds1_;
-                                        length = ds_ + ds1_, from = index[0];
-                                        index[0] = bm_, index[1] = bk_;
-                                        altitude = b_alt_, elevation[0] = b_e0_, elevation[1] = b_e1_;
-                                        state_ = ST_STEP_;
+                                if (o.located) { /* [ref stepper.c:861-863] */
+                                        x[0] = x[0] + d[0] * b_.ds1, x[1] = x[1] + d[1] * b_.ds1, x[2] = x[2] + d[2] * b_.ds1;
+                                        length = ds_ + b_.ds1, from = index[0];
+                                        index[0] = b_.bm, index[1] = b_.bk;
+                                        altitude = b_.b_alt, elevation[0] = b_.b_e0, elevation[1] = b_.b_e1;
+                                        state_ = ST_STEP;
                                         event = CROSSING;
                                 }
                         }
@@ -1940,10 +1970,9 @@ struct Stepping {
         }
 
 private:
-        enum { ST_ORIGIN_ = 0, ST_STEP_ = 1, ST_HALVE_ = 2 };
-        int state_, halvings_, bm_, bk_;
-        double ds_, ds0_, ds1_;
-        double b_alt_, b_e0_, b_e1_; /* the halving's last sample of the other medium */
+        int state_;
+        double ds_;
+        Bisection b_;
         Cell cell_;
 };
 

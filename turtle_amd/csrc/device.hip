@@ -35,9 +35,19 @@
  *                   modes held to 128 registers)
  *   k_bisect        ... and bisected here, packed [ref stepper.c:836-864]
  *   k_gradient, k_project   batch gradients and map projections
- *   k_trace         persistent-wave trace-to-boundary loop (the hot kernel)
+ *   k_trace         persistent-wave trace-to-boundary loop (the hot kernel: trace_body)
  *   k_first         a fast trace's first closed-form steps, flat: a ray a lane
- *   k_isotropic     Philox-4x32-10 isotropic directions (scattering harness)
+ *   k_cross         the crossings a trace's passes listed, located by halving
+ *   k_ray_cells     the cell each ray starts over: the key a large trace orders its rays by
+ *   k_walk          a whole scattering walk per ray, in registers (turtle_stepper_scatter_n)
+ *   k_traverse      a line of sight per ray through every medium, every tile resident
+ *                   (turtle_stepper_traverse_n; <REC>: turtle_stepper_crossings_n)
+ *   k_traverse_gen, k_crossings_gen   the same over paged stacks: the accounting after each
+ *                   generation of k_step + k_bisect
+ *   k_resample      a whole map from a stack or a map (turtle_map_resample)
+ *   k_fill_encode, k_fill_store, k_nodes   windows of nodes (turtle_map_fill_n, _node_n)
+ *   k_unblock       the host copy of a map from its HBM copy
+ *   k_isotropic, k_philox   Philox-4x32-10: isotropic directions, raw words (scattering harness)
  *   k_tally         hit counts + path-length histogram (uint64, exact)
  */
 #include <hip/hip_runtime.h>
@@ -65,6 +75,52 @@ namespace {
 __device__ __forceinline__ int lane_rank(ull mask)
 {
         return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+}
+
+/* The ray queue of k_walk: a counter in HBM from which a wave draws `chunk` ray numbers at a time
+ * with one atomic (wave-aggregated), so the queue sees n / chunk atomics.  (trace_body keeps a
+ * refill of its own: the paged wait, the pool and the ordered input are woven in.  So does
+ * k_traverse, and its own copy of the step machine: see there.) */
+struct RayQueue {
+        long next = 0, end = 0; /* wave-uniform: the numbers drawn and not yet given to a lane */
+        bool exhausted = false; /* wave-uniform: the queue has run dry */
+};
+
+/* Refill the idle lanes (ray < 0 and not `dead`), whole wave: a lane gets its number in `ray` and
+ * take() loads that ray -- or sets `ray` below 0 again for one with nothing to do, and the lane
+ * draws again.  A lane that still needs a ray when the queue is dry is `dead`. */
+template <class Take>
+__device__ __forceinline__ void queue_refill(RayQueue & q, ull * __restrict__ queue, int chunk, long n,
+    long & ray, bool & dead, Take && take)
+{
+        for (;;) {
+                const bool need = (ray < 0) && !dead;
+                const ull mask = __ballot(need);
+                if (mask == 0) break;
+                if (q.next >= q.end) {
+                        if (q.exhausted) {
+                                if (need) dead = true;
+                                break;
+                        }
+                        ull base = 0;
+                        if ((threadIdx.x & 63) == 0) base = atomicAdd(queue, (ull)chunk);
+                        base = __shfl(base, 0, 64);
+                        q.next = (long)base;
+                        q.end = min((long)base + chunk, n);
+                        if ((long)base >= n) {
+                                q.exhausted = true;
+                                q.next = q.end = 0;
+                        }
+                        continue;
+                }
+                const long avail = q.end - q.next;
+                const int rank = lane_rank(mask);
+                if (need && (rank < avail)) {
+                        ray = q.next + rank;
+                        take();
+                }
+                q.next += min((long)__popcll(mask), avail);
+        }
 }
 
 /* ======================================================================== */
@@ -1027,8 +1083,6 @@ constexpr int kCreepBackoff = CREEP_BACKOFF; /* general iterations a busy wave w
 #endif
 constexpr int kRelayBatch = TRACE_RELAY_BATCH;       /* lanes of a busy wave that a closed form waits for ... */
 constexpr int kRelayPatience = TRACE_RELAY_PATIENCE; /* ... at most this many general iterations */
-
-enum { ST_INIT = 0, ST_STEP = 1, ST_BISECT = 2 };
 
 /* Persistent waves; one ray per lane; ONE sample per lane per iteration.
  *
@@ -2546,8 +2600,7 @@ __global__ void __launch_bounds__(256) WALK_WAVES_ATTR k_walk(tamd_view v, long 
     double * __restrict__ length, int * __restrict__ steps, WalkIO io, ull * __restrict__ stats,
     ull * __restrict__ queue)
 {
-        long pool_next = 0, pool_end = 0; /* wave-uniform */
-        bool exhausted = false;            /* wave-uniform */
+        RayQueue q;
         OneCtx ctx;
         d_load_ctx<MODE, FAST>(v, ctx);
         CellCache cell = { ~0u, 0u, 0u, -1, nullptr };
@@ -2557,91 +2610,53 @@ __global__ void __launch_bounds__(256) WALK_WAVES_ATTR k_walk(tamd_view v, long 
         bool dead = false;
         int state = ST_STEP, count = 0;
         double bx = 0, by = 0, bz = 0, dx = 0, dy = 0, dz = 0, len = 0;
-        double ds = 0, ds0 = 0, ds1 = 0;
+        double ds = 0;
         double s_alt = 0, s_e0 = 0, s_e1 = 0; /* the sample the ray stands on */
-        double b_alt = 0, b_e0 = 0, b_e1 = 0; /* the bisection's last sample of the new medium */
-        int m = -1, k = -1, bm = -1, bk = -1, halvings = 0;
+        Bisection b = { 0., 0., 0., 0., 0., -1, -1, 0 };
+        int m = -1, k = -1;
         ull my_rays = 0, my_steps = 0, my_samples = 0, my_plain = 0;
 
         for (;;) {
-                /* ---- refill idle lanes from the queue (as k_trace) ---- */
-                for (;;) {
-                        const bool need = (ray < 0) && !dead;
-                        const ull mask = __ballot(need);
-                        if (mask == 0) break;
-                        if (pool_next >= pool_end) {
-                                if (exhausted) {
-                                        if (need) dead = true;
-                                        break;
-                                }
-                                ull base = 0;
-                                if ((threadIdx.x & 63) == 0) base = atomicAdd(queue, (ull)kChunk);
-                                base = __shfl(base, 0, 64);
-                                pool_next = (long)base;
-                                pool_end = min((long)base + kChunk, n);
-                                if ((long)base >= n) {
-                                        exhausted = true;
-                                        pool_next = pool_end = 0;
-                                }
-                                continue;
+                queue_refill(q, queue, kChunk, n, ray, dead, [&] {
+                        m = index[2 * ray], k = index[2 * ray + 1];
+                        if ((m < 0) || (io.n_steps <= 0)) {
+                                ray = -1; /* has left the data: no further step */
+                        } else {
+                                bx = pos[3 * ray], by = pos[3 * ray + 1], bz = pos[3 * ray + 2];
+                                s_alt = alt[ray], s_e0 = elev[2 * ray], s_e1 = elev[2 * ray + 1];
+                                /* the sum goes on where it stands: the same roundings
+                                 * in one call as in several */
+                                len = length[ray], count = 0, state = ST_STEP;
+                                ds = d_step_length(v, s_alt, s_e0, s_e1, m);
+                                d_isotropic((ull)(io.first + ray), (ull)io.first_step, io.seed, dx, dy, dz);
                         }
-                        const long avail = pool_end - pool_next;
-                        const int rank = lane_rank(mask);
-                        if (need && (rank < avail)) {
-                                ray = pool_next + rank;
-                                m = index[2 * ray], k = index[2 * ray + 1];
-                                if ((m < 0) || (io.n_steps <= 0)) {
-                                        ray = -1; /* has left the data: no further step */
-                                } else {
-                                        bx = pos[3 * ray], by = pos[3 * ray + 1], bz = pos[3 * ray + 2];
-                                        s_alt = alt[ray], s_e0 = elev[2 * ray], s_e1 = elev[2 * ray + 1];
-                                        /* the sum goes on where it stands: the same roundings
-                                         * in one call as in several */
-                                        len = length[ray], count = 0, state = ST_STEP;
-                                        ds = d_step_length(v, s_alt, s_e0, s_e1, m);
-                                        d_isotropic((ull)(io.first + ray), (ull)io.first_step, io.seed, dx, dy, dz);
-                                }
-                        }
-                        pool_next += min((long)__popcll(mask), avail);
-                }
+                });
                 if (__ballot(ray >= 0) == 0) {
-                        if (exhausted) break;
+                        if (q.exhausted) break;
                         continue; /* (every ray drawn had left the data: draw again) */
                 }
                 if (ray >= 0) {
                         /* ---- one sample at q = B + d * t ---- */
-                        const double t = (state == ST_STEP) ? ds : 0.5 * (ds0 + ds1);
+                        const bool stepping = (state == ST_STEP);
+                        const double t = stepping ? ds : 0.5 * (b.ds0 + b.ds1);
                         const double qx = bx + dx * t, qy = by + dy * t, qz = bz + dz * t;
                         Sample s;
                         d_sample<MODE, FAST>(v, ctx, qx, qy, qz, s, cache);
                         my_samples++;
-                        /* ---- bookkeeping: STEP and BISECT together, as selects (k_trace) ---- */
-                        const bool stepping = (state == ST_STEP);
-                        const bool same = (s.m == m);
-                        const bool accept = stepping & same;
-                        const bool cross = stepping & !same;
-                        const bool other = !same;
-                        bx = stepping ? qx : bx, by = stepping ? qy : by, bz = stepping ? qz : bz;
-                        bm = other ? s.m : bm, bk = other ? s.k : bk;
-                        b_alt = other ? s.alt : b_alt, b_e0 = other ? s.e0 : b_e0, b_e1 = other ? s.e1 : b_e1;
-                        ds0 = cross ? -ds : ((!stepping & same) ? t : ds0);
-                        ds1 = cross ? 0. : ((!stepping & other) ? t : ds1);
-                        halvings = stepping ? 0 : halvings + 1;
-                        state = cross ? ST_BISECT : state;
+                        /* ---- bookkeeping: the step machine of turtle_amd_device.h ---- */
+                        const StepOutcome o = step_or_bisect(b, state, bx, by, bz, m, ds, t, qx, qy, qz, s);
                         my_steps += stepping ? 1 : 0;
-                        my_plain += accept ? 1 : 0;
-                        const bool located = (state == ST_BISECT) & !cross &
-                            (!(ds1 - ds0 > 1E-08) | (halvings > 1200));
-                        bool ended = accept;
-                        if (accept) {
+                        my_plain += o.accept ? 1 : 0;
+                        bool ended = o.accept;
+                        if (o.accept) {
                                 len += ds, k = s.k;
                                 s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
                         }
-                        if (located) { /* [ref stepper.c:861-863] */
-                                bx = bx + dx * ds1, by = by + dy * ds1, bz = bz + dz * ds1;
-                                len += ds + ds1;
-                                m = bm, k = bk;
-                                s_alt = b_alt, s_e0 = b_e0, s_e1 = b_e1;
+                        if (o.located) { /* [ref stepper.c:861-863] */
+                                bx = bx + dx * b.ds1, by = by + dy * b.ds1, bz = bz + dz * b.ds1;
+                                len += ds + b.ds1;
+                                m = b.bm, k = b.bk;
+                                s_alt = b.b_alt, s_e0 = b.b_e0, s_e1 = b.b_e1;
                                 state = ST_STEP;
                                 ended = true;
                         }
@@ -2681,7 +2696,13 @@ __global__ void __launch_bounds__(256) WALK_WAVES_ATTR k_walk(tamd_view v, long 
  * medium's total loaded from length[m'][r] -- one load and one store a crossing,
  * the reference's order of additions, and registers independent of the number
  * of media.  Every lane ends through max_steps, the halving guard or the queue
- * running dry. */
+ * running dry.
+ * The kernel keeps its OWN copy of the refill loop (queue_refill) and of the select block
+ * (step_or_bisect, turtle_amd_device.h), expression for expression: built on the shared ones its
+ * 12 instances kept their resources and their results, but scripts/exp_traverse.py measured
+ * three of four figures outside the margin (profiles/step_machine_ab.txt).  A change to either
+ * has to be made here too; tests/test_gpu_device_api.py and test_gpu_step_machine.py hold this
+ * copy to Stepping::trip(), which runs the shared one, bit for bit. */
 struct TraverseIO {
         const double * __restrict__ dir;
         double * __restrict__ length; /* [media][n], zeroed by the driver; or NULL */
@@ -2724,7 +2745,7 @@ __global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * 
         ull my_rays = 0, my_steps = 0, my_samples = 0, my_capped = 0;
 
         for (;;) {
-                /* ---- refill idle lanes from the queue (as k_walk) ---- */
+                /* ---- refill idle lanes from the queue (queue_refill's loop, spelt out) ---- */
                 for (;;) {
                         const bool need = (ray < 0) && !dead;
                         const ull mask = __ballot(need);
@@ -2774,7 +2795,7 @@ __global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * 
                                 state = ST_STEP;
                                 ended = true;
                         } else {
-                                /* ---- bookkeeping: STEP and BISECT together, as selects (k_walk) ---- */
+                                /* ---- bookkeeping: step_or_bisect()'s selects, spelt out ---- */
                                 const bool same = (s.m == m);
                                 const bool accept = stepping & same;
                                 const bool cross = stepping & !same;
