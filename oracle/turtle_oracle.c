@@ -484,10 +484,11 @@ void orc_stepper_init(struct orc_stepper * s, const struct orc_geometry * geomet
 /* stepper.c:602-615 */
 void orc_stepper_reset(struct orc_stepper * s)
 {
-        int i;
+        int i, t;
         for (i = 0; i < 3; i++) {
                 s->last.position[i] = DBL_MAX;
-                s->reference_ecef[i] = DBL_MAX;
+                for (t = 0; t < ORC_MAX_TRANSFORMS; t++)
+                        s->transform[t].reference_ecef[i] = DBL_MAX;
         }
 }
 
@@ -507,33 +508,70 @@ static void exact_geodetic(
         }
 }
 
-/* stepper.c:85-171, for the one "geodetic" transform (n0 = 0, n1 = 3) */
-static void get_geographic(
-    struct orc_stepper * s, const double * position, double * geo)
+/* compute_geodetic (proj NULL) and compute_geomap, stepper.c:57-83 */
+static void compute_geographic(struct orc_stepper * s,
+    const struct orc_proj * proj, const double * position, int n0, double * geo)
 {
-        if (s->local_range <= 0.) { /* stepper.c:97-106 */
-                exact_geodetic(s, position, geo);
+        if ((proj == NULL) || (n0 == 0)) exact_geodetic(s, position, geo);
+        if (proj != NULL) orc_project(proj, geo[0], geo[1], geo + 3, geo + 4);
+}
+
+/* The slot of a projection's transform, by name (stepper.c:336-355): the
+ * parsed projection stands for its name.  NULL: "geodetic". */
+static struct orc_transform * transform_of(
+    struct orc_stepper * s, const struct orc_proj * proj)
+{
+        if (proj == NULL) return &s->transform[0];
+        int t;
+        for (t = 1; t < ORC_MAX_TRANSFORMS - 1; t++) {
+                struct orc_transform * q = &s->transform[t];
+                if (!q->used) {
+                        q->used = 1;
+                        q->proj = *proj;
+                        return q;
+                }
+                if ((q->proj.type == proj->type) &&
+                    (q->proj.lambert_tag == proj->lambert_tag) &&
+                    (q->proj.longitude_0 == proj->longitude_0) &&
+                    (q->proj.hemisphere == proj->hemisphere))
+                        return q;
+        }
+        return &s->transform[t]; /* (more names than slots: the last is shared) */
+}
+
+/* stepper.c:85-171: coordinates n0 .. n1 - 1 of `geo` by the transform `tr`
+ * (proj NULL: the "geodetic" one, n0 = 0, n1 = 3; else n1 = 5) */
+static void get_geographic(struct orc_stepper * s, struct orc_transform * tr,
+    const struct orc_proj * proj, const double * position, int n0, int n1,
+    double * geo)
+{
+        int i, j;
+        if (tr->updated) { /* stepper.c:91-95 */
+                memcpy(geo + n0, tr->history + n0, (n1 - n0) * sizeof(double));
                 return;
+        }
+        if (s->local_range <= 0.) { /* stepper.c:97-106 */
+                compute_geographic(s, proj, position, n0, geo);
+                goto backup;
         }
 
         double local[3], range = 0.;
-        int i, j;
         for (i = 0; i < 3; i++) { /* stepper.c:109-116 */
-                double r = position[i] - s->reference_ecef[i];
+                double r = position[i] - tr->reference_ecef[i];
                 local[i] = r;
                 r = fabs(r);
                 if (r > range) range = r;
         }
         if (range < s->local_range) { /* stepper.c:118-128 */
-                for (i = 0; i < 3; i++) {
-                        geo[i] = s->reference_geographic[i];
+                for (i = n0; i < n1; i++) {
+                        geo[i] = tr->reference_geographic[i];
                         for (j = 0; j < 3; j++)
-                                geo[i] += s->jacobian[i][j] * local[j];
+                                geo[i] += tr->jacobian[i][j] * local[j];
                 }
-                return;
+                goto backup;
         }
 
-        exact_geodetic(s, position, geo); /* stepper.c:131-133 */
+        compute_geographic(s, proj, position, n0, geo); /* stepper.c:131-133 */
 
         double step = 0.; /* stepper.c:138-142 */
         for (i = 0; i < 3; i++) {
@@ -541,18 +579,21 @@ static void get_geographic(
                 if (d > step) step = d;
         }
         if (step < 0.33 * s->local_range) { /* stepper.c:144-162 */
-                memcpy(s->reference_ecef, position, sizeof(s->reference_ecef));
-                memcpy(s->reference_geographic, geo,
-                    sizeof(s->reference_geographic));
+                memcpy(tr->reference_ecef, position, sizeof(tr->reference_ecef));
+                memcpy(tr->reference_geographic + n0, geo + n0,
+                    (n1 - n0) * sizeof(double));
                 for (i = 0; i < 3; i++) {
                         double r[3] = { position[0], position[1], position[2] };
                         r[i] += 10.;
-                        double geo1[3];
-                        exact_geodetic(s, r, geo1);
-                        for (j = 0; j < 3; j++)
-                                s->jacobian[j][i] = 0.1 * (geo1[j] - geo[j]);
+                        double geo1[5];
+                        compute_geographic(s, proj, r, 0, geo1);
+                        for (j = n0; j < n1; j++)
+                                tr->jacobian[j][i] = 0.1 * (geo1[j] - geo[j]);
                 }
         }
+backup: /* stepper.c:165-168 */
+        memcpy(tr->history + n0, geo + n0, (n1 - n0) * sizeof(double));
+        tr->updated = 1;
 }
 
 /* Elevation of one data source at (lat, lon): stepper.c:199-264 (step form)
@@ -596,6 +637,9 @@ static int stepper_sample(struct orc_stepper * s, const double * position,
         }
 
         s->n_samples++;
+        int t;
+        for (t = 0; t < ORC_MAX_TRANSFORMS; t++) /* stepper.c:674-680, :712 */
+                s->transform[t].updated = 0;
         sample->index[0] = sample->index[1] = -1; /* stepper.c:713-716 */
         sample->elevation[0] = -DBL_MAX;
         sample->elevation[1] = DBL_MAX;
@@ -605,17 +649,32 @@ static int stepper_sample(struct orc_stepper * s, const double * position,
                 for (k = G->layer_first[layer]; k < G->layer_first[layer + 1];
                      k++, data_index++) {
                         const struct orc_meta * m = &G->metas[k];
-                        if (!has_geodetic) {
-                                get_geographic(s, position, sample->geographic);
-                                if (sample == &s->last) /* stepper.c:730-733 */
-                                        memcpy(s->last.position, position,
-                                            sizeof(s->last.position));
-                                has_geodetic = 1;
-                        }
+                        const struct orc_grid * g =
+                            (m->kind == ORC_MAP) ? &G->grids[m->src] : NULL;
                         double elevation;
-                        const int inside = source_elevation(G, m,
-                            sample->geographic[0], sample->geographic[1],
-                            &elevation);
+                        int inside;
+                        if ((g != NULL) && (g->proj.type >= 0)) {
+                                /* stepper.c:242-248: its own transform, with
+                                 * the geodetic part when none came before */
+                                get_geographic(s, transform_of(s, &g->proj),
+                                    &g->proj, position, has_geodetic ? 3 : 0, 5,
+                                    sample->geographic);
+                                inside = orc_grid_elevation(g,
+                                    sample->geographic[3],
+                                    sample->geographic[4], &elevation);
+                        } else {
+                                if (!has_geodetic)
+                                        get_geographic(s, transform_of(s, NULL),
+                                            NULL, position, 0, 3,
+                                            sample->geographic);
+                                inside = source_elevation(G, m,
+                                    sample->geographic[0],
+                                    sample->geographic[1], &elevation);
+                        }
+                        if (sample == &s->last) /* stepper.c:730-733 */
+                                memcpy(s->last.position, position,
+                                    sizeof(s->last.position));
+                        has_geodetic = 1;
                         if (!inside) continue;
                         elevation += m->offset; /* stepper.c:737 */
                         if (elevation >= sample->geographic[2]) {

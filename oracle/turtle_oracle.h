@@ -86,20 +86,32 @@ struct orc_geometry {
 /* src/turtle/stepper.h:93-98 */
 struct orc_sample {
         double position[3];
-        double geographic[3]; /* lat, lon, alt */
+        double geographic[5]; /* lat, lon, alt, and the last projected map's x, y */
         double elevation[2];
         int index[2];
 };
 
-/* src/turtle/stepper.h:45-58 (the single "geodetic" transform) and :101-110 */
+/* src/turtle/stepper.h:45-58: the local linear approximation of one transform
+ * (stepper.c:85-171) and what it gave at the current sample */
+struct orc_transform {
+        int used;
+        struct orc_proj proj; /* the projection that names it (slot 0: "geodetic") */
+        double reference_ecef[3];
+        double reference_geographic[5];
+        double jacobian[5][3];
+        int updated;
+        double history[5];
+};
+#define ORC_MAX_TRANSFORMS 8
+
+/* src/turtle/stepper.h:101-110.  The data of a stepper share a transform by NAME
+ * (stepper.c:332-362): "geodetic" for flats, stacks and maps without a projection
+ * (slot 0), the projection's name for a projected map (a slot each, as met). */
 struct orc_stepper {
         const struct orc_geometry * geometry;
         double local_range, slope_factor, resolution_factor;
         struct orc_sample last;
-        /* Local linear approximation state (stepper.c:85-171) */
-        double reference_ecef[3];
-        double reference_geographic[3];
-        double jacobian[3][3];
+        struct orc_transform transform[ORC_MAX_TRANSFORMS];
         /* counters (not in the reference): exact transforms and samples */
         long n_transforms, n_samples;
 };

@@ -257,3 +257,49 @@ def test_g12_rough_and_void_ground(golden):
     e, geodetic = RC.deep_transforms(O.ecef_from_geodetic, O.ecef_to_geodetic)
     assert RC.sha(e) == str(g["deep_ecef_sha"]) and RC.sha(geodetic) == str(g["deep_geodetic_sha"])
     assert (geodetic[2] < -25e3 + 1).all() and (geodetic[2] > -40e3 - 1).all()
+
+
+def test_g14_composite_geometries(golden):
+    """Traces at both local ranges, lines of sight through every medium, and position and single
+    steps hugging every rim, over composite geometries (tests/composite_cases.py: a stack beside
+    maps and flats, overlapping maps, layers without data, a geoid): the restatement against the
+    reference (composite.npz), bit for bit, NaN for NaN"""
+    import composite_cases as CC
+    import traverse_cases as TC
+    g = golden("composite")
+    lat, lon = CC.utm_footprint()       # the UTM map lies inside tile (0N, 11E)
+    assert (lat > 0.0).all() and (lat < 1.0).all() and (lon > 11.0).all() and (lon < 12.0).all()
+    for case in CC.CASES:
+        assert CC.nodes_sha(case) == str(g[f"{case}_nodes_sha"])
+        geo = CC.oracle_geometry(case)
+        pos, d, _ = CC.graze(case, geo, CC.GOLDEN_RAYS)
+        assert CC.sha(pos) == str(g[f"{case}_graze_origin_sha"])
+        assert CC.sha(d) == str(g[f"{case}_graze_direction_sha"])
+        for tag, local_range in (("r1", 1.0), ("r0", 0.0)):
+            k = f"{case}_{tag}_"
+            t = geo.trace(pos, d, max_steps=CC.GRAZE_MAX_STEPS, local_range=local_range, threads=4)
+            assert eq(t["index"], g[k + "index"].astype(np.int32)), k
+            assert eq(t["n_steps"], g[k + "n_steps"]) and eq(t["length"], g[k + "length"]), k
+            assert eq(t["position"], g[k + "position"]), k
+        pos, d = CC.sight(case, CC.GOLDEN_RAYS)
+        k = f"{case}_sight_"
+        assert CC.sha(pos) == str(g[k + "origin_sha"]) and CC.sha(d) == str(g[k + "direction_sha"])
+        t = TC.check(geo, pos, d, CC.CEILING, max_steps=CC.SIGHT_MAX_STEPS, threads=4)
+        assert eq(t["index"], g[k + "index"].astype(np.int32)), k
+        assert eq(t["length"], g[k + "length"]) and eq(t["n_steps"], g[k + "n_steps"]), k
+        assert eq(t["n_crossings"], g[k + "n_crossings"]), k
+        k = f"{case}_rim_"
+        lat, lon, _ = CC.rim_points(case)
+        assert CC.sha(np.stack([lat, lon])) == str(g[k + "points_sha"])
+        both = set()
+        for layer in range(len(CC.RECIPES[case][1]) - 1):
+            p, di = geo.position(lat, lon, 100.0, layer=layer)
+            assert eq(di, g[k + f"data{layer}"].astype(np.int32)), (k, layer)
+            assert eq(p[di >= 0], g[k + f"position{layer}"][di >= 0]), (k, layer)
+            both |= set(np.unique(di))
+        assert len(both) >= 3           # the points do hug rims: more than one data answers
+        start = O.ecef_from_geodetic(lat, lon, np.full(lat.size, 2500.0))
+        assert CC.sha(start) == str(g[k + "start_sha"])
+        o, rows = geo.step(start), g[k + "step"]
+        assert eq(o["latitude"], rows[:, 0]) and eq(o["longitude"], rows[:, 1]) and eq(o["altitude"], rows[:, 2])
+        assert eq(o["elevation"], rows[:, 3:5]) and eq(o["index"], rows[:, 5:7].astype(np.int32)), k
