@@ -48,7 +48,9 @@
  *   k_fill_encode, k_fill_store, k_nodes   windows of nodes (turtle_map_fill_n, _node_n)
  *   k_unblock       the host copy of a map from its HBM copy
  *   k_isotropic, k_philox   Philox-4x32-10: isotropic directions, raw words (scattering harness)
- *   k_tally         hit counts + path-length histogram (uint64, exact)
+ *   k_order_count, k_order_place   a trace's hand-over list in the order of its one-byte keys: a
+ *                   counting sort between the two passes
+ *   k_tally         hit counts + path-length histogram (uint64, exact): a block a CU at the most
  */
 #include <hip/hip_runtime.h>
 #include <hipcub/device/device_radix_sort.hpp>
@@ -2953,35 +2955,161 @@ __global__ void k_isotropic(long n, ull seed, ull stream, long first, double * _
 }
 
 /* hits[m + 1] and a linear path-length histogram, exact integer counts.
- * Per-block LDS counters (32-bit) flushed with one 64-bit atomic per bin. */
-__global__ void __launch_bounds__(256) k_tally(long n, const int * __restrict__ index,
+ * Per-block LDS counters (32-bit) flushed with one 64-bit atomic per non-zero bin -- from at most a
+ * block a CU (tamd_k_tally), since what such a launch costs is the adds that meet on one word in
+ * HBM: a bin that every block holds sees a few hundred of them, not thousands.
+ * The hits of a few media (kTallyBallotMedia: every real geometry) never meet in LDS either, where a
+ * wave's 64 adds to one or two words would queue: a ballot per medium, and lane j of a wave keeps
+ * the wave's count of medium j - 1 in a register until the end.  The histogram is in LDS, in
+ * `copies` copies that the block's waves share out among themselves (as many as fit: the launcher). */
+constexpr int kTallyThreads = 1024;
+constexpr int kTallyBallotMedia = 7;
+
+__global__ void __launch_bounds__(kTallyThreads) k_tally(long n, const int * __restrict__ index,
     const double * __restrict__ length, int n_media, ull * __restrict__ hits,
-    int n_bins, double scale, ull * __restrict__ histogram)
+    int n_bins, double scale, ull * __restrict__ histogram, int copies)
 {
         extern __shared__ unsigned int lds[];
         unsigned int * h_hits = lds;                 /* n_media + 1 */
-        unsigned int * h_bins = lds + (n_media + 1); /* n_bins + 1 */
-        const int total = n_media + 1 + n_bins + 1;
+        unsigned int * h_bins = lds + (n_media + 1); /* copies x (n_bins + 1) */
+        const int total = n_media + 1 + copies * (n_bins + 1);
         for (int i = threadIdx.x; i < total; i += blockDim.x) lds[i] = 0;
         __syncthreads();
-        for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
-             r += (long)gridDim.x * blockDim.x) {
-                const int m = index[2 * r];
-                if ((m >= -1) && (m < n_media)) atomicAdd(&h_hits[m + 1], 1u);
-                const double t = length[r] * scale;
-                int b = n_bins; /* overflow, also NaN and negatives */
-                if ((t >= 0.) && (t < (double)n_bins)) b = (int)t;
-                atomicAdd(&h_bins[b], 1u);
+        const int lane = threadIdx.x & 63;
+        unsigned int * my_bins = h_bins + (size_t)((threadIdx.x >> 6) % copies) * (n_bins + 1);
+        const bool by_ballot = (n_media <= kTallyBallotMedia);
+        unsigned int my_hits = 0; /* lane j: this wave's rays in medium j - 1 */
+        /* (a wave at a time: its lanes stay together for the ballots) */
+        for (long first = blockIdx.x * (long)blockDim.x + (threadIdx.x - lane); first < n;
+             first += (long)gridDim.x * blockDim.x) {
+                const long r = first + lane;
+                const bool live = (r < n);
+                int m = -2; /* (counted nowhere) */
+                if (live) {
+                        m = index[2 * r];
+                        const double t = length[r] * scale;
+                        int b = n_bins; /* overflow, also NaN and negatives */
+                        if ((t >= 0.) && (t < (double)n_bins)) b = (int)t;
+                        atomicAdd(&my_bins[b], 1u);
+                }
+                if (by_ballot) {
+                        for (int j = 0; j <= n_media; j++) {
+                                const unsigned int c = (unsigned int)__popcll(__ballot(m + 1 == j));
+                                if (lane == j) my_hits += c;
+                        }
+                } else if ((m >= -1) && (m < n_media))
+                        atomicAdd(&h_hits[m + 1], 1u);
+        }
+        if (by_ballot && (lane <= n_media) && (my_hits != 0)) atomicAdd(&h_hits[lane], my_hits);
+        __syncthreads();
+        for (int i = threadIdx.x; i < n_media + 1 + n_bins + 1; i += blockDim.x) {
+                if (i <= n_media) {
+                        if (h_hits[i] != 0) atomicAdd(&hits[i], (ull)h_hits[i]);
+                        continue;
+                }
+                const int b = i - (n_media + 1);
+                unsigned int c = 0;
+                for (int k = 0; k < copies; k++) c += h_bins[(size_t)k * (n_bins + 1) + b];
+                if (c != 0) atomicAdd(&histogram[b], (ull)c);
+        }
+}
+
+/* ---- the ordered hand-over ---------------------------------------------------
+ * The front [0, F) of a trace's hand-over list in the order of its one-byte keys (where phase A
+ * parks: the shallowest rays first), the back [n - K, n) as it is: a counting sort in two flat
+ * kernels, between the two passes (hand_over_sort).  F and K are read from the passes' counters on
+ * the device; the places between the two ends are holes, known by their position, and nothing
+ * reads them or their keys.  Both kernels give block b the same contiguous chunk of the front.
+ * k_order_count adds up how many of each key there are (an LDS histogram a block, then one add per
+ * non-zero bin to the 256 `counts`); k_order_place scans those for where each key's ids begin,
+ * counts its chunk again, reserves its share of each bin with one returning add on the bin's cursor
+ * and places its ids there.  Rays with EQUAL keys come out in whatever order the adds fell: the
+ * list itself is filled by atomics, in no fixed order, and no result depends on the order the
+ * lined pass draws its rays in (test_sorted_hand_over_changes_no_bit).  Nothing waits, spins or
+ * polls.  counts and cursors: zeroed by the caller (tamd_k_trace's one fill). */
+constexpr int kOrderThreads = 1024;
+constexpr int kOrderBlocks = 256;
+constexpr int kOrderBins = TAMD_ORDER_BINS;
+
+struct OrderSpan {
+        long n_front, n_back; /* F, K: within the list whatever the counters say */
+        long lo, hi;          /* this block's chunk of the front */
+};
+__device__ __forceinline__ OrderSpan order_span(long n, const ull * __restrict__ n_front,
+    const ull * __restrict__ n_back)
+{
+        OrderSpan s;
+        s.n_front = min((long)min(*n_front, (ull)n), n);
+        s.n_back = (n_back != nullptr) ? (long)min(*n_back, (ull)(n - s.n_front)) : 0;
+        /* (a multiple of 16 places: a chunk's keys begin on a word) */
+        const long chunk = ((s.n_front + gridDim.x - 1) / gridDim.x + 15) & ~15L;
+        s.lo = min(s.n_front, blockIdx.x * chunk);
+        s.hi = min(s.n_front, s.lo + chunk);
+        return s;
+}
+/* f(place, key) for every place of [lo, hi), four keys a load (lo is a multiple of 4, as the keys'
+ * address) */
+template <class F>
+__device__ __forceinline__ void order_each(const unsigned char * __restrict__ keys, long lo, long hi, F && f)
+{
+        for (long i = lo + 4L * threadIdx.x; i < hi; i += 4L * blockDim.x) {
+                if (i + 4 <= hi) {
+                        const unsigned int four = *(const unsigned int *)(keys + i);
+                        for (int k = 0; k < 4; k++) f(i + k, (int)((four >> (8 * k)) & 255u));
+                } else
+                        for (long j = i; j < hi; j++) f(j, (int)keys[j]);
+        }
+}
+
+__global__ void __launch_bounds__(kOrderThreads) k_order_count(long n, const unsigned char * __restrict__ keys,
+    const ull * __restrict__ n_front, const ull * __restrict__ n_back, unsigned int * __restrict__ counts)
+{
+        __shared__ unsigned int mine[kOrderBins];
+        const OrderSpan s = order_span(n, n_front, n_back);
+        if (s.lo >= s.hi) return; /* (block-uniform) */
+        if (threadIdx.x < kOrderBins) mine[threadIdx.x] = 0;
+        __syncthreads();
+        order_each(keys, s.lo, s.hi, [&](long, int key) { atomicAdd(&mine[key], 1u); });
+        __syncthreads();
+        if ((threadIdx.x < kOrderBins) && (mine[threadIdx.x] != 0)) atomicAdd(&counts[threadIdx.x], mine[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(kOrderThreads) k_order_place(long n, const unsigned char * __restrict__ keys,
+    const int * __restrict__ ids, const ull * __restrict__ n_front, const ull * __restrict__ n_back,
+    const unsigned int * __restrict__ counts, unsigned int * __restrict__ cursors, int * __restrict__ out)
+{
+        __shared__ unsigned int mine[kOrderBins]; /* this chunk's ids of each key; then where the next goes */
+        __shared__ unsigned int wave_sum[kOrderBins / 64];
+        const OrderSpan s = order_span(n, n_front, n_back);
+        /* the back, as it is */
+        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < s.n_back; i += (long)gridDim.x * blockDim.x)
+                out[n - s.n_back + i] = ids[n - s.n_back + i];
+        if (s.lo >= s.hi) return; /* (block-uniform) */
+        const int t = threadIdx.x, lane = t & 63;
+        if (t < kOrderBins) mine[t] = 0;
+        __syncthreads();
+        order_each(keys, s.lo, s.hi, [&](long, int key) { atomicAdd(&mine[key], 1u); });
+        /* where each key's ids begin: the exclusive scan of the counts, a wave over 64 bins */
+        const unsigned int count = (t < kOrderBins) ? counts[t] : 0;
+        unsigned int upto = count;
+        for (int d = 1; d < 64; d <<= 1) {
+                const unsigned int below = __shfl_up(upto, d, 64);
+                if (lane >= d) upto += below;
+        }
+        if ((t < kOrderBins) && (lane == 63)) wave_sum[t >> 6] = upto;
+        __syncthreads();
+        if (t < kOrderBins) {
+                unsigned int begin = upto - count;
+                for (int w = 0; w < (t >> 6); w++) begin += wave_sum[w];
+                const unsigned int held = mine[t];
+                const unsigned int taken = (held != 0) ? atomicAdd(&cursors[t], held) : 0;
+                mine[t] = begin + taken;
         }
         __syncthreads();
-        for (int i = threadIdx.x; i < total; i += blockDim.x) {
-                const unsigned int c = lds[i];
-                if (c == 0) continue;
-                if (i <= n_media)
-                        atomicAdd(&hits[i], (ull)c);
-                else
-                        atomicAdd(&histogram[i - (n_media + 1)], (ull)c);
-        }
+        order_each(keys, s.lo, s.hi, [&](long place, int key) {
+                const unsigned int to = atomicAdd(&mine[key], 1u);
+                if ((long)to < s.n_front) out[to] = ids[place];
+        });
 }
 
 /* ---- turtle_map_resample ------------------------------------------------------
@@ -3247,6 +3375,21 @@ static int launch_items(const char * name, void (*kernel)(P...), long n, size_t 
         if (tamd_dev_init()) return 1;
         if (n <= 0) return 0;
         return launch_blocks(name, kernel, grid_for(n, 256), lds_bytes, args...);
+}
+
+/* What a launcher zeroes before its kernels: the first n_stats words of `stats` (0: none, they add
+ * up over the rounds of a call) and the first n_queue of `queue`.  A fill is a launch of its own,
+ * 5 us between two dependent kernels: the two are ONE where they are neighbours, as in a stepper's
+ * d_stats (internal.h: TAMD_STATS_QUEUE). */
+static int zero_words(ull * stats, int n_stats, ull * queue, int n_queue)
+{
+        if ((n_stats > 0) && (queue == stats + TAMD_STATS_QUEUE) && (n_stats <= TAMD_STATS_QUEUE)) {
+                HIP_TRY(hipMemsetAsync(stats, 0, (size_t)(TAMD_STATS_QUEUE + n_queue) * sizeof(ull), g_stream));
+                return 0;
+        }
+        if (n_stats > 0) HIP_TRY(hipMemsetAsync(stats, 0, (size_t)n_stats * sizeof(ull), g_stream));
+        HIP_TRY(hipMemsetAsync(queue, 0, (size_t)n_queue * sizeof(ull), g_stream));
+        return 0;
 }
 
 /* A run-time value that a kernel takes as a template parameter: f is called with the
@@ -3606,6 +3749,20 @@ static int sort_hand_over(long n)
         if (value == 1) return 1;
         return n <= ((value > 1) ? value : 4000000L);
 }
+/* ... and by which sort: the counting sort of the library's own (k_order_count, k_order_place: two
+ * kernels, no fill of the keys, nothing of its own to zero) or hipCUB's radix sort (three kernels on
+ * one 8-bit pass, fills of its own, and the keys pre-filled so that the holes sort between the two
+ * ends).  The same rays reach the lined pass in the same order of keys either way; ties may differ,
+ * and no result depends on them (tests/test_gpu_sort_own.py).  Measured, one MI355X, the time from
+ * phase A's end to the lined pass's start, hipCUB's -> the library's own: one map at 1 / 2 / 4 M rays
+ * 50.2 -> 22.5, 56.9 -> 28.2, 62.9 -> 38.1 us; a 4 x 4 stack at 1 M rays 53.7 -> 24.1.  So: the
+ * library's own for every batch the hand-over is ordered for.
+ * TURTLE_AMD_SORT_OWN=0 / 1: hipCUB's / the library's own (unset: the rule). */
+static int sort_own(void)
+{
+        static Knob knob = { "TURTLE_AMD_SORT_OWN", 1 };
+        return knob.get() != 0;
+}
 /* Does a trace take its rays in the order of where they start (k_ray_cells)?  TURTLE_AMD_SPATIAL:
  * 0 never, 1 always, else from that many rays on. */
 static int spatial_order(int mode, long n)
@@ -3768,11 +3925,12 @@ static int order_rays(struct tamd_view view, long n, char * room, const tamd_tra
 
 /* The hand-over of a first round (a later round of a paged trace takes rays at any step count:
  * one end, unsorted).  The list is filled from both ends (sort_long_if(); PhaseIO).  And its front
- * may be ORDERED: keys beside the list, a radix sort of the whole list's n places between
- * the two passes -- places nobody filled carry a key (254) between the front's (0 .. 253) and the
- * back's (255), so the front comes out first, in order, and the back stays at the far end, where
- * the lined pass looks for it.  For batches small enough to be as long as their longest rays
- * (sort_hand_over()).  Planned before phase A, which writes the keys ... */
+ * may be ORDERED between the two passes, by one-byte keys beside the list (0 .. 253; the back's are
+ * 255): by the library's counting sort of the front (k_order_count; sort_own()), which leaves the
+ * back where the lined pass looks for it -- or by a radix sort of the whole list's n places, where
+ * the places nobody filled carry a key (254) between the front's and the back's, so the front comes
+ * out first, in order, and the back stays at the far end.  For batches small enough to be as long
+ * as their longest rays (sort_hand_over()).  Planned before phase A, which writes the keys ... */
 static int hand_over_plan(RoomSort<unsigned char> & sort, long n, bool again, ull * queue, double * ds_mark,
     PhaseIO & a, PhaseIO & b, bool & sorting)
 {
@@ -3782,15 +3940,38 @@ static int hand_over_plan(RoomSort<unsigned char> & sort, long n, bool again, ul
         a.n_parked_back = counter_of(queue, TAMD_TRACE_N_PARKED_BACK);
         a.ds_mark = ds_mark, a.mark_at = a.park_after / 2, a.long_if = (float)long_if;
         b.n_dev_back = a.n_parked_back;
-        sorting = sort_hand_over(n) && sort.fits();
+        sorting = sort_hand_over(n) && (sort_own() || sort.fits());
         if (!sorting) return 0;
         a.sort_key = sort.keys.Current();
-        HIP_TRY(hipMemsetAsync(a.sort_key, 0xFE, (size_t)n, g_stream));
+        if (!sort_own()) HIP_TRY(hipMemsetAsync(a.sort_key, 0xFE, (size_t)n, g_stream));
+        return 0;
+}
+/* The two kernels of the counting sort: ids and keys as phase A left them, n_front and n_back its
+ * counters, `words` the 2 x 256 zeroed words of the ordering (internal.h).  At most a block a CU's
+ * worth (256), each with 4096 places or more of the front -- if the front were the whole list. */
+static int launch_order(long n, const int * ids, const unsigned char * keys, const ull * n_front, const ull * n_back,
+    unsigned int * words, int * out)
+{
+        const long wanted = (n + 4 * kOrderThreads - 1) / (4 * kOrderThreads);
+        const unsigned blocks = (unsigned)((wanted < 1) ? 1 : (wanted > kOrderBlocks) ? kOrderBlocks : wanted);
+        hipLaunchKernelGGL(k_order_count, dim3(blocks), dim3(kOrderThreads), 0, g_stream, n, keys, n_front, n_back,
+            words);
+        LAUNCH_CHECK("k_order_count");
+        hipLaunchKernelGGL(k_order_place, dim3(blocks), dim3(kOrderThreads), 0, g_stream, n, keys, ids, n_front,
+            n_back, words, words + kOrderBins, out);
+        LAUNCH_CHECK("k_order_place");
         return 0;
 }
 /* ... and run behind it: the lined pass reads the ordered list */
-static int hand_over_sort(RoomSort<unsigned char> & sort, PhaseIO & b)
+static int hand_over_sort(RoomSort<unsigned char> & sort, long n, const PhaseIO & a, ull * queue, PhaseIO & b)
 {
+        if (sort_own()) {
+                if (launch_order(n, sort.ids.Current(), sort.keys.Current(), a.n_parked, a.n_parked_back,
+                        (unsigned int *)(queue + TAMD_TRACE_COUNTERS), sort.ids.Alternate()))
+                        return 1;
+                b.ids = sort.ids.Alternate();
+                return 0;
+        }
         if (sort.run()) return 1;
         b.ids = sort.ids.Current();
         return 0;
@@ -3903,7 +4084,7 @@ static int run_trace(struct tamd_view view, long n, TraceRays rays, int max_step
         bool sorting = false;
         if (hand_over_plan(hand_over, n, again, queue, TAMD_ROOM_AT(double, room, at.ds_mark), a, b, sorting)) return 1;
         if (launch_phase_a<MODE>(view, n, again, rays, max_steps, flags, a, out, stats, queue)) return 1;
-        if (sorting && hand_over_sort(hand_over, b)) return 1;
+        if (sorting && hand_over_sort(hand_over, n, a, queue, b)) return 1;
         if (launch_lined<MODE>(view, n, rays, max_steps, flags, b, tail, stats, queue)) return 1;
         return launch_cross<MODE, true>(view, n, rays, cross, pg, stats, out, tail);
 }
@@ -3926,8 +4107,7 @@ extern "C" int tamd_k_trace(struct tamd_view view, long n, double * pos,
                 snprintf(g_error, sizeof(g_error), "tamd_k_trace: a required array is missing");
                 return 1;
         }
-        if (pg.ids == nullptr) HIP_TRY(hipMemsetAsync(stats, 0, 4 * sizeof(ull), g_stream));
-        HIP_TRY(hipMemsetAsync(queue, 0, TAMD_TRACE_COUNTERS * sizeof(ull), g_stream));
+        if (zero_words(stats, (pg.ids == nullptr) ? 4 : 0, queue, TAMD_TRACE_QUEUE_WORDS)) return 1;
         if (n <= 0) return 0;
         const int carry = (flags & TURTLE_AMD_TRACE_RESUME) ? TRACE_CARRY_MEDIUM : 0;
         const TraceRays rays = { pos, dir, index, length, n_steps };
@@ -3944,8 +4124,7 @@ extern "C" int tamd_k_step_dir(struct tamd_view view, long n, double * pos,
     struct tamd_paging pg, unsigned long long * stats, unsigned long long * queue)
 {
         if (tamd_dev_init()) return 1;
-        if (pg.ids == nullptr) HIP_TRY(hipMemsetAsync(stats, 0, 4 * sizeof(ull), g_stream));
-        HIP_TRY(hipMemsetAsync(queue, 0, 3 * sizeof(ull), g_stream));
+        if (zero_words(stats, (pg.ids == nullptr) ? 4 : 0, queue, 3)) return 1;
         if (n <= 0) return 0;
         const CrossList cross = { cross_ray, (cross_ray != nullptr) ? cross_ds : nullptr, queue + 2, nullptr };
         const StepWalk no_walk = { 0, 0, 0, 0, nullptr, nullptr };
@@ -4008,8 +4187,7 @@ extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, cons
     const struct tamd_crossings * rec, unsigned long long * stats, unsigned long long * queue)
 {
         if (tamd_dev_init()) return 1;
-        HIP_TRY(hipMemsetAsync(stats, 0, 4 * sizeof(ull), g_stream));
-        HIP_TRY(hipMemsetAsync(queue, 0, sizeof(ull), g_stream));
+        if (zero_words(stats, 4, queue, 1)) return 1;
         if (n <= 0) return 0;
         const TraverseIO io = { dir, length, n_steps, n_cross, ceiling, max_steps };
         const bool strict = g_math_strict || !view.fast_ok;
@@ -4075,8 +4253,37 @@ extern "C" int tamd_k_tally(long n, const int * index, const double * length,
                 return 1;
         }
         const double scale = (double)n_bins / length_max;
-        return launch_blocks("k_tally", k_tally, grid_for(n, 256), lds, n, index, length, n_media, hits, n_bins, scale,
-            histogram);
+        /* a block a CU at the most, a ray a thread at the least; as many copies of the histogram as
+         * the block has waves, or as fit beside the hits in the 64 KB a launch may ask for.  (C2's 1 M
+         * rays, 2 media, 1 024 bins: 10.0 us; on eight 256-thread blocks a CU, the hits by LDS adds:
+         * 47.7 us) */
+        static Knob block = { "TURTLE_AMD_TALLY_THREADS", kTallyThreads }; /* (experiments: 256, 512) */
+        const int threads = ((block.get() == 256) || (block.get() == 512)) ? (int)block.get() : kTallyThreads;
+        const long cus = (g_cus > 0) ? g_cus : 256;
+        long blocks = (n + threads - 1) / threads;
+        if (blocks > cus) blocks = cus;
+        const size_t one = (size_t)(n_bins + 1) * sizeof(unsigned int);
+        size_t copies = (64 * 1024 - (size_t)(n_media + 1) * sizeof(unsigned int)) / one;
+        if (copies > (size_t)threads / 64) copies = (size_t)threads / 64;
+        hipLaunchKernelGGL(k_tally, dim3((unsigned)blocks), dim3(threads),
+            (size_t)(n_media + 1) * sizeof(unsigned int) + copies * one, g_stream, n, index, length, n_media, hits,
+            n_bins, scale, histogram, (int)copies);
+        LAUNCH_CHECK("k_tally");
+        return 0;
+}
+
+/* the ordering of a hand-over list on its own (run_trace has it between its passes): see
+ * k_order_count; words: 2 x 256 x 32 bits, zeroed by the caller */
+extern "C" int tamd_k_hand_over_order(long n, const int * ids, const unsigned char * keys,
+    const unsigned long long * n_front, const unsigned long long * n_back, unsigned int * words, int * out)
+{
+        if (tamd_dev_init()) return 1;
+        if (n <= 0) return 0;
+        if ((ids == nullptr) || (keys == nullptr) || (n_front == nullptr) || (words == nullptr) || (out == nullptr)) {
+                snprintf(g_error, sizeof(g_error), "tamd_k_hand_over_order: a required array is missing");
+                return 1;
+        }
+        return launch_order(n, ids, keys, n_front, n_back, words, out);
 }
 
 extern "C" int tamd_k_resample(struct tamd_view view, const struct tamd_grid * grids, int from_map,

@@ -151,14 +151,30 @@ enum tamd_trace_counter {
 };
 #define TAMD_TRACE_COUNTER_STRIDE 16
 #define TAMD_TRACE_COUNTERS (TAMD_TRACE_N_COUNTERS * TAMD_TRACE_COUNTER_STRIDE)
+/* Behind the counters, in the same `queue`: the words of the ordered hand-over (k_order_count,
+ * k_order_place) -- 256 bin counts, then 256 bin cursors, 32 bits each -- so that one fill zeroes
+ * them with the counters. */
+#define TAMD_ORDER_BINS 256
+#define TAMD_TRACE_ORDER_WORDS (2 * TAMD_ORDER_BINS * 4 / 8) /* in uint64 words */
+#define TAMD_TRACE_QUEUE_WORDS (TAMD_TRACE_COUNTERS + TAMD_TRACE_ORDER_WORDS)
 /* A stepper's words on the device (host.h: d_stats): the 4 stats of its last batch call, the
- * `queue` of the launchers (a trace's counters; the others use its first three words), and the
- * step kernels' own stats of a paged traverse, which keeps its sums in the first 4 meanwhile. */
+ * `queue` of the launchers (a trace's counters and ordering words; the others use its first three
+ * words), and the step kernels' own stats of a paged traverse, which keeps its sums in the first 4
+ * meanwhile.  stats and queue are contiguous: a launcher that zeroes both does it in one fill. */
 #define TAMD_STATS_QUEUE 4
-#define TAMD_STATS_STEPS (TAMD_STATS_QUEUE + TAMD_TRACE_COUNTERS)
+#define TAMD_STATS_ORDER (TAMD_STATS_QUEUE + TAMD_TRACE_COUNTERS)
+#define TAMD_STATS_STEPS (TAMD_STATS_QUEUE + TAMD_TRACE_QUEUE_WORDS)
 #define TAMD_STATS_WORDS (TAMD_STATS_STEPS + 4)
-/* stats: 4 x uint64 on the device (rays, steps, samples, capped); queue: TAMD_TRACE_COUNTERS x
- * uint64 (enum tamd_trace_counter); both zeroed by the launcher.
+#if defined(__cplusplus)
+static_assert(TAMD_STATS_ORDER + TAMD_TRACE_ORDER_WORDS == TAMD_STATS_STEPS,
+    "stats, the trace's counters and the ordering's words are one contiguous run of d_stats");
+#else
+_Static_assert(TAMD_STATS_ORDER + TAMD_TRACE_ORDER_WORDS == TAMD_STATS_STEPS,
+    "stats, the trace's counters and the ordering's words are one contiguous run of d_stats");
+#endif
+/* stats: 4 x uint64 on the device (rays, steps, samples, capped); queue: TAMD_TRACE_QUEUE_WORDS x
+ * uint64 (enum tamd_trace_counter, then the ordering's words); both zeroed by the launcher, in one
+ * fill where queue == stats + TAMD_STATS_QUEUE.
  * room: the stepper's scratch block, laid out for THIS n by tamd_trace_room_layout() (trace_room.h: the
  * lists of rays handed from pass to pass, the sorts' room, the ordered copies), or NULL for a
  * single-pass launch that bisects in place; with it, length and n_steps must not be NULL.  (The
@@ -168,6 +184,13 @@ int tamd_k_trace(struct tamd_view view, long n, double * pos,
     const double * dir, int max_steps, int * index, double * length,
     int * n_steps, int flags, void * room, struct tamd_paging pg,
     unsigned long long * stats, unsigned long long * queue);
+/* The ordering of a trace's hand-over list, as tamd_k_trace runs it between its passes: of `ids`
+ * (n places) and the one-byte `keys` beside them, the front's *n_front ids into out[0, *n_front) in
+ * non-decreasing order of their keys (equal keys in any order) and the back's *n_back ids (NULL:
+ * none) into out[n - *n_back, n) as they are; the places between are not written.  words: 2 x
+ * TAMD_ORDER_BINS 32-bit words, zeroed by the caller. */
+int tamd_k_hand_over_order(long n, const int * ids, const unsigned char * keys,
+    const unsigned long long * n_front, const unsigned long long * n_back, unsigned int * words, int * out);
 /* a flag of the step kernels beside enum turtle_amd_step_flags: `alt` holds the tentative length
  * of the next step instead of the altitude, `elev` is not used (turtle_stepper_walk_n) */
 #define TAMD_STEP_COMPACT 0x200
