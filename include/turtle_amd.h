@@ -915,7 +915,82 @@ TURTLE_API enum turtle_return turtle_stepper_crossings_n(
     double * distance /* [capacity][n] or NULL */, int * media /* [capacity][n][2] or NULL */,
     int space);
 
-/* Totals of the LAST trace_n, scatter_n, traverse_n or crossings_n call on this stepper,
+/* Why turtle_stepper_advance_n stopped a ray. */
+enum turtle_amd_advance_status {
+        TURTLE_AMD_ADVANCE_SPENT = 0,     /* the depth budget ran out (or was <= 0, or NaN, at the origin) */
+        TURTLE_AMD_ADVANCE_DISTANCE = 1,  /* distance_max was reached */
+        TURTLE_AMD_ADVANCE_LEFT = 2,      /* the ray left the data (or started outside it) */
+        TURTLE_AMD_ADVANCE_CEILING = 3,   /* altitude >= altitude_max */
+        TURTLE_AMD_ADVANCE_MAX_STEPS = 4
+};
+
+/* Rays advanced by a column-depth budget: turtle_stepper_traverse_n's loop, which the physics may
+ * stop before the geometry does -- after the column depth budget[r] (the sum of density[medium] x
+ * path: a muon's range, the grammage to an interaction) or at the distance distance_max[r] (the
+ * other end of a chord).  density has turtle_amd_stepper_media(stepper) elements and lies, like
+ * every array of the call, in `space`.  For each ray r, exactly (a fresh stepper history per ray;
+ * B = budget[r], M = distance_max ? distance_max[r] : HUGE_VAL):
+ *
+ *     turtle_stepper_step(s, pos, NULL, NULL, NULL, &alt, NULL, NULL, idx);  X = 0; d = 0; steps = 0;
+ *     for (;;) {
+ *             if (idx[0] < 0)            { status = LEFT; break; }
+ *             if (!(X < B))              { status = SPENT; break; }
+ *             if (!(d < M))              { status = DISTANCE; break; }
+ *             if (!(alt < altitude_max)) { status = CEILING; break; }
+ *             if (steps >= max_steps)    { status = MAX_STEPS; break; }
+ *             m = idx[0]; k = idx[1]; p0 = pos;                      (the step starts in medium m)
+ *             turtle_stepper_step(s, pos, dir, NULL, NULL, &alt, NULL, &ds, idx);
+ *             x = density[m] * ds;
+ *             spent = (X + x >= B);  far = (d + ds >= M);
+ *             if (spent || far) {                 (the step is cut short: by the model it lies in medium m)
+ *                     f = ds;  status = SPENT;
+ *                     if (far)   { f = M - d; status = DISTANCE; }
+ *                     if (spent) { fs = (B - X) / density[m]; if (fs <= f) { f = fs; status = SPENT; } }
+ *                     if (f > ds) f = ds;                            (a rounding guard)
+ *                     pos[j] = p0[j] + dir[j] * f;                   (a product, then a sum)
+ *                     if (status == SPENT) { X = B; d += f; } else { X += density[m] * f; d = M; }
+ *                     steps++; idx[0] = m; idx[1] = k; break;
+ *             }
+ *             X += x; d += ds; steps++;
+ *     }
+ *     index[r] = idx; depth[r] = X; distance[r] = d; n_steps[r] = steps; status[r] = status;
+ *
+ * (`status = SPENT` before the two ifs decides the one case they leave open: spent alone, with fs
+ * rounded above ds.)  What follows from it, and is tested:
+ *  - with budget = HUGE_VAL, distance_max = NULL and finite densities, position, index and n_steps
+ *    are bit for bit those of turtle_stepper_traverse_n on the same inputs: the tests on a ray are
+ *    traverse's, in traverse's order, and the budget tests never fire; distance is then the bits of
+ *    the last recorded distance of turtle_stepper_crossings_n for a ray that left the data;
+ *  - with every density equal to 1, depth == distance to the bit on every ray that no cut stopped;
+ *  - a density of 0 (vacuum) never spends anything, and a division by it cannot happen: spent needs
+ *    x > 0;
+ *  - densities and budgets are not checked (as turtle_stepper_clearance_n does not check its
+ *    fractions); a NaN budget stops the ray at its origin as SPENT;
+ *  - point to point: direction the unit vector from p to t and distance_max = |t - p|; status
+ *    DISTANCE then means that the chord lies inside the data and under the ceiling, depth is the
+ *    column depth between the two points, and with density = {1, 0, ...} the rock between them;
+ *  - after a cut the ray stands INSIDE medium index[r][0], not on a boundary: a later call from that
+ *    position starts from a fresh sample.
+ * Arithmetic follows turtle_amd_math_set as turtle_stepper_traverse_n does; crossings are located
+ * by halving in either mode, and the cut itself (fs, f, the position, X, d) is plain IEEE arithmetic
+ * in the order stated.  depth, distance, n_steps and distance_max may be NULL: which outputs a
+ * caller asks for changes no bit of the others.  BAD_ADDRESS: stepper, position, direction, density,
+ * budget, index or status NULL; DOMAIN_ERROR: max_steps < 0 or an unknown space (both before a
+ * device is touched: nothing changes); n <= 0 does nothing.  Every tile of every stack has to be
+ * in memory, as for turtle_stepper_horizon_n: the call loads what is missing and fails with
+ * DOMAIN_ERROR where a stack's stack_size is below its number of tiles (a cut needs the position
+ * a step began at, which the paged, generation-by-generation form does not keep).
+ * turtle_amd_stepper_rounds reports 1, turtle_stepper_trace_stats reports the call as it does
+ * traverse_n.  In DEVICE space the call only queues work. */
+TURTLE_API enum turtle_return turtle_stepper_advance_n(
+    struct turtle_stepper * stepper, long n, double * position /* [n][3], in / out */,
+    const double * direction /* [n][3] */, const double * density /* [media] */,
+    const double * budget /* [n] */, const double * distance_max /* [n] or NULL */,
+    double altitude_max, int max_steps, int * index /* [n][2], out */,
+    double * depth /* [n] or NULL */, double * distance /* [n] or NULL */,
+    int * n_steps /* [n] or NULL */, int * status /* [n], mandatory */, int space);
+
+/* Totals of the LAST trace_n, scatter_n, traverse_n, crossings_n or advance_n call on this stepper,
  * accumulated on the device: stats[0] rays, [1] steps, [2] samples (transform +
  * layer lookup; the same from run to run), [3] rays that stopped at max_steps.
  * Synchronises the stream. */

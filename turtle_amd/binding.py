@@ -21,6 +21,8 @@ TRACE_RESUME = 1
 SCATTER_START = 1
 RESAMPLE_CLAMP = 1
 FILL_CLAMP = 1
+# enum turtle_amd_advance_status: why turtle_stepper_advance_n stopped a ray
+ADVANCE_SPENT, ADVANCE_DISTANCE, ADVANCE_LEFT, ADVANCE_CEILING, ADVANCE_MAX_STEPS = range(5)
 
 RETURN_NAMES = [
     "SUCCESS", "BAD_ADDRESS", "BAD_EXTENSION", "BAD_FORMAT", "BAD_PROJECTION",
@@ -861,6 +863,36 @@ class Stepper:
                                                 _ptr(distance), _ptr(media), sp))
         return dict(position=pos, index=index, length=length, n_steps=nsteps,
                     n_crossings=ncross, point=point, distance=distance, media=media)
+
+    def advance(self, position, direction, density, budget, distance_max=None,
+                altitude_max=float("inf"), max_steps=1000000, want=("depth", "distance", "n_steps")):
+        """turtle_stepper_advance_n -> dict(position, index, depth, distance, n_steps, status): each
+        ray stepped as traverse steps it until its column depth (the sum of density[medium] x
+        path) reaches budget[r], its path reaches distance_max[r] (None: no limit), or the
+        geometry stops it; `status` says which (ADVANCE_SPENT ... ADVANCE_MAX_STEPS).  `density`
+        has `media` elements.  The position advances in place (as in traverse)."""
+        sp = _space_of(position, direction, density, budget, distance_max)
+        pos = _as(position, sp).reshape(-1, 3)
+        d = _as(direction, sp).reshape(-1, 3)
+        n = pos.shape[0]
+        rho = _as(density, sp).reshape(-1)
+        if rho.shape[0] != self.media:
+            raise ValueError(f"density has {rho.shape[0]} elements for {self.media} media")
+        b = _as(budget, sp).reshape(-1)
+        dmax = None if distance_max is None else _as(distance_max, sp).reshape(-1)
+        if b.shape[0] != n or (dmax is not None and dmax.shape[0] != n):
+            raise ValueError("budget and distance_max have one element a ray")
+        index = _new((n, 2), sp, np.int32, like=pos)
+        depth = _new((n,), sp, like=pos) if "depth" in want else None
+        distance = _new((n,), sp, like=pos) if "distance" in want else None
+        nsteps = _new((n,), sp, np.int32, like=pos) if "n_steps" in want else None
+        status = _new((n,), sp, np.int32, like=pos)
+        _check(lib().turtle_stepper_advance_n(self.h, C.c_long(n), _ptr(pos), _ptr(d), _ptr(rho), _ptr(b),
+                                              _ptr(dmax), C.c_double(altitude_max), int(max_steps),
+                                              _ptr(index), _ptr(depth), _ptr(distance), _ptr(nsteps),
+                                              _ptr(status), sp))
+        return dict(position=pos, index=index, depth=depth, distance=distance, n_steps=nsteps,
+                    status=status)
 
     def view(self):
         """turtle_amd_stepper_view_acquire / _release as a context manager: `with st.view() as v`

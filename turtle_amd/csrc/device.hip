@@ -2866,6 +2866,160 @@ __global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * 
         block_tally(stats, my_rays, my_steps, my_samples, my_capped);
 }
 
+/* ---- a ray advanced by a column-depth budget ----------------------------------
+ *
+ * turtle_stepper_advance_n over a geometry with every tile resident: traverse_n's
+ * loop (include/turtle_amd.h states it), one ray per lane, with two more ways to
+ * end: the column depth X = sum of density[medium] x step has reached the ray's
+ * budget B, or the path d its limit M.  Built on the shared machine as k_walk is
+ * (queue_refill, step_or_bisect), with k_traverse's third state for the origin
+ * sample.  An EVENT is an accepted step or a located crossing: there, and only
+ * there, the lane does the definition's bookkeeping with the density of the medium
+ * the step started in (read from density[] when the ray enters a medium: a load at
+ * every step sat on each lane's chain); while it halves a crossing
+ * nothing is tested, and the step's full length ds + ds1 is one value
+ * (k_traverse<REC>'s tot += ds + ds1: the same bits).  A step that would reach B or
+ * M is cut short: the ray ends at p0 + dir * f, p0 the position the step began at.
+ * A lane keeps X, d, B, M and that density over what a k_traverse lane keeps; p0
+ * costs nothing: for an accepted step it is the trip's own starting point, and
+ * while a crossing is halved it lies in the registers of the sample the ray stood
+ * on, which is dead by then.  The tests after an event are traverse's in
+ * traverse's order with the two budget tests between them; with B = inf and no M
+ * they never fire: the bits of k_traverse. */
+struct AdvanceIO {
+        const double * __restrict__ dir;
+        const double * __restrict__ density;  /* [media] */
+        const double * __restrict__ budget;   /* [n] */
+        const double * __restrict__ dist_max; /* [n] or NULL */
+        double * __restrict__ depth;          /* or NULL */
+        double * __restrict__ distance;       /* or NULL */
+        int * __restrict__ n_steps;           /* or NULL */
+        int * __restrict__ status;
+        double ceiling;
+        int max_steps;
+};
+
+template <int MODE, bool FAST>
+__global__ void __launch_bounds__(256) k_advance(tamd_view v, long n, double * __restrict__ pos,
+    int * __restrict__ index, AdvanceIO io, ull * __restrict__ stats, ull * __restrict__ queue)
+{
+        RayQueue q;
+        OneCtx ctx;
+        d_load_ctx<MODE, FAST>(v, ctx);
+        CellCache cell = { ~0u, 0u, 0u, -1, nullptr };
+        CellCache * cache = (FAST && (MODE != TAMD_MODE_GENERIC)) ? &cell : nullptr;
+
+        long ray = -1;
+        bool dead = false;
+        int state = ST_INIT, count = 0;
+        double bx = 0, by = 0, bz = 0, dx = 0, dy = 0, dz = 0;
+        double X = 0, d = 0, B = 0, M = 0;
+        double rho = 0; /* density[m]: read when the ray enters a medium, not at every step */
+        double ds = 0;
+        /* the sample the ray stands on -- and, while it halves a crossing (ds is set, the sample
+         * no longer needed: an event replaces it), the position p0 its step began at */
+        double s_alt = 0, s_e0 = 0, s_e1 = 0;
+        Bisection b = { 0., 0., 0., 0., 0., -1, -1, 0 };
+        int m = -1, k = -1;
+        ull my_rays = 0, my_steps = 0, my_samples = 0, my_capped = 0;
+
+        for (;;) {
+                queue_refill(q, queue, kChunk, n, ray, dead, [&] {
+                        bx = pos[3 * ray], by = pos[3 * ray + 1], bz = pos[3 * ray + 2];
+                        dx = io.dir[3 * ray], dy = io.dir[3 * ray + 1], dz = io.dir[3 * ray + 2];
+                        B = io.budget[ray];
+                        M = (io.dist_max != nullptr) ? io.dist_max[ray] : HUGE_VAL;
+                        state = ST_INIT, count = 0, X = 0., d = 0.;
+                });
+                if (__ballot(ray >= 0) == 0) break; /* (a lane that drew nothing is dead: so are all) */
+                if (ray >= 0) {
+                        /* ---- one sample at q = B + d * t (the origin itself first) ---- */
+                        const bool init = (state == ST_INIT);
+                        const bool stepping = (state == ST_STEP);
+                        const double t = stepping ? ds : 0.5 * (b.ds0 + b.ds1);
+                        const double qx = init ? bx : bx + dx * t, qy = init ? by : by + dy * t,
+                                     qz = init ? bz : bz + dz * t;
+                        Sample s;
+                        d_sample<MODE, FAST>(v, ctx, qx, qy, qz, s, cache);
+                        my_samples++;
+                        bool event = false;
+                        int status = -1; /* set: the ray ends */
+                        if (init) { /* [ref stepper.c:780-796] the loop's first call */
+                                m = s.m, k = s.k;
+                                s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
+                                if (m >= 0) rho = io.density[m];
+                                state = ST_STEP;
+                                event = true;
+                        } else {
+                                /* ---- bookkeeping: the step machine of turtle_amd_device.h ---- */
+                                const double ox = bx, oy = by, oz = bz; /* (stepping: where the step begins) */
+                                const StepOutcome o = step_or_bisect(b, state, bx, by, bz, m, ds, t, qx, qy, qz, s);
+                                my_steps += stepping ? 1 : 0;
+                                event = o.accept | o.located;
+                                if (stepping & !o.accept) s_alt = ox, s_e0 = oy, s_e1 = oz; /* p0, kept for the halving */
+                                if (event) {
+                                        const double p0x = o.accept ? ox : s_alt, p0y = o.accept ? oy : s_e0,
+                                                     p0z = o.accept ? oz : s_e1;
+                                        /* the step's full length, in the medium m it started in */
+                                        const double len = o.located ? ds + b.ds1 : ds;
+                                        const double x = rho * len;
+                                        const bool spent = (X + x >= B), far = (d + len >= M);
+                                        count++;
+                                        if (spent | far) { /* the step is cut short, inside medium m */
+                                                double f = far ? M - d : len;
+                                                status = far ? TURTLE_AMD_ADVANCE_DISTANCE : TURTLE_AMD_ADVANCE_SPENT;
+                                                if (spent) {
+                                                        const double fs = (B - X) / rho;
+                                                        if (fs <= f) f = fs, status = TURTLE_AMD_ADVANCE_SPENT;
+                                                }
+                                                if (f > len) f = len; /* (a rounding guard) */
+                                                bx = p0x + dx * f, by = p0y + dy * f, bz = p0z + dz * f;
+                                                const bool by_depth = (status == TURTLE_AMD_ADVANCE_SPENT);
+                                                X = by_depth ? B : X + rho * f;
+                                                d = by_depth ? d + f : M;
+                                        } else {
+                                                X += x, d += len;
+                                                if (o.accept) {
+                                                        k = s.k;
+                                                        s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
+                                                } else { /* [ref stepper.c:861-863] */
+                                                        bx = bx + dx * b.ds1, by = by + dy * b.ds1, bz = bz + dz * b.ds1;
+                                                        m = b.bm, k = b.bk;
+                                                        s_alt = b.b_alt, s_e0 = b.b_e0, s_e1 = b.b_e1;
+                                                        if (m >= 0) rho = io.density[m];
+                                                }
+                                        }
+                                        state = ST_STEP;
+                                }
+                        }
+                        if (event) { /* a step is over (or the origin sampled): the loop's tests */
+                                if (status < 0) {
+                                        if (m < 0) status = TURTLE_AMD_ADVANCE_LEFT;
+                                        else if (!(X < B)) status = TURTLE_AMD_ADVANCE_SPENT;
+                                        else if (!(d < M)) status = TURTLE_AMD_ADVANCE_DISTANCE;
+                                        /* (s_alt, s_e0, s_e1: after an event always the sample again, never p0) */
+                                        else if (!(s_alt < io.ceiling)) status = TURTLE_AMD_ADVANCE_CEILING;
+                                        else if (count >= io.max_steps) status = TURTLE_AMD_ADVANCE_MAX_STEPS;
+                                }
+                                if (status >= 0) {
+                                        pos[3 * ray] = bx, pos[3 * ray + 1] = by, pos[3 * ray + 2] = bz;
+                                        index[2 * ray] = m, index[2 * ray + 1] = k;
+                                        if (io.depth != nullptr) io.depth[ray] = X;
+                                        if (io.distance != nullptr) io.distance[ray] = d;
+                                        if (io.n_steps != nullptr) io.n_steps[ray] = count;
+                                        io.status[ray] = status;
+                                        my_rays++;
+                                        my_capped += (status == TURTLE_AMD_ADVANCE_MAX_STEPS) ? 1 : 0;
+                                        ray = -1;
+                                } else {
+                                        ds = d_step_length(v, s_alt, s_e0, s_e1, m);
+                                }
+                        }
+                }
+        }
+        block_tally(stats, my_rays, my_steps, my_samples, my_capped);
+}
+
 /* After one generation of a paged traverse (or, `first`, after the origins were
  * sampled): the step each live ray took added to the sum of the medium it
  * started in, the loop's test, and the rays it ends taken out of the stepping
@@ -4196,6 +4350,27 @@ extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, cons
                 if (rec != nullptr)
                         return launch_traverse<MODE, true>(view, n, pos, index, io, stats, queue, strict, *rec);
                 return launch_traverse<MODE, false>(view, n, pos, index, io, stats, queue, strict, NoCrossings());
+        });
+}
+
+/* A whole advance in one launch (k_advance): every tile resident, nothing listed */
+extern "C" int tamd_k_advance(struct tamd_view view, long n, double * pos, const double * dir,
+    const double * density, const double * budget, const double * distance_max, double ceiling,
+    int max_steps, int * index, double * depth, double * distance, int * n_steps, int * status,
+    unsigned long long * stats, unsigned long long * queue)
+{
+        if (tamd_dev_init()) return 1;
+        if (zero_words(stats, 4, queue, 1)) return 1;
+        if (n <= 0) return 0;
+        const AdvanceIO io = { dir, density, budget, distance_max, depth, distance, n_steps, status, ceiling,
+                max_steps };
+        const bool strict = g_math_strict || !view.fast_ok;
+        return with_mode(view.mode, [&](auto mode) {
+                return with_math(strict, [&](auto fast) {
+                        const auto kernel = k_advance<decltype(mode)::value, decltype(fast)::value>;
+                        return launch_blocks("k_advance", kernel, persistent_blocks(kernel, n), 0, view, n, pos,
+                            index, io, stats, queue);
+                });
         });
 }
 

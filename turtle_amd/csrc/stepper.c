@@ -1450,6 +1450,69 @@ enum turtle_return turtle_stepper_crossings_n(struct turtle_stepper * stepper, l
             length, n_steps, n_crossings, &rec, space);
 }
 
+/* turtle_stepper_advance_n: resident tiles only (a cut needs the position its step began at, which
+ * the generation kernels overwrite): one launch through stepper_resident, and sight_run's closing
+ * sequence over a stage of its own. */
+struct advance_args {
+        struct tamd_stage stage;
+        int paged; /* out: a tile was not resident when the tables were made current */
+        long n;
+        void *pos, *dir, *density, *budget, *distance_max, *index, *depth, *distance, *n_steps, *status;
+        double ceiling;
+        int max_steps;
+};
+
+static int advance_resident(struct turtle_stepper * stepper, struct tamd_paging pg, int round, void * p)
+{
+        struct advance_args * a = p;
+        (void)pg, (void)round;
+        if ((a->paged = stepper_is_paged(stepper))) return 0; /* (a tile another thread took meanwhile) */
+        return tamd_k_advance(stepper->view, a->n, a->pos, a->dir, a->density, a->budget, a->distance_max,
+            a->ceiling, a->max_steps, a->index, a->depth, a->distance, a->n_steps, a->status, stepper->d_stats,
+            stepper->d_stats + TAMD_STATS_QUEUE);
+}
+
+enum turtle_return turtle_stepper_advance_n(struct turtle_stepper * stepper, long n, double * position,
+    const double * direction, const double * density, const double * budget, const double * distance_max,
+    double altitude_max, int max_steps, int * index, double * depth, double * distance, int * n_steps,
+    int * status, int space)
+{
+        TAMD_ERROR_INIT(&turtle_stepper_advance_n);
+        if ((stepper == NULL) || (position == NULL) || (direction == NULL) || (density == NULL) ||
+            (budget == NULL) || (index == NULL) || (status == NULL))
+                return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
+        if (max_steps < 0) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid input parameter(s)");
+        if ((space != TURTLE_AMD_HOST) && (space != TURTLE_AMD_DEVICE))
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid space (%d)", space);
+        if (n <= 0) return TURTLE_RETURN_SUCCESS;
+        const enum turtle_return loaded =
+            stepper_load_all(stepper, &error_, turtle_error_function(error_.function), "advances over");
+        if (loaded != TURTLE_RETURN_SUCCESS) return loaded;
+        struct advance_args a = { 0 };
+        struct tamd_stage * st = &a.stage;
+        a.n = n, a.ceiling = altitude_max, a.max_steps = max_steps;
+        const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int);
+        const size_t media = (size_t)stepper->n_layers + 1;
+        tamd_stage_add(st, position, 3 * nb, TAMD_INOUT, &a.pos);
+        tamd_stage_add(st, direction, 3 * nb, TAMD_IN, &a.dir);
+        tamd_stage_add(st, density, media * sizeof(double), TAMD_IN, &a.density);
+        tamd_stage_add(st, budget, nb, TAMD_IN, &a.budget);
+        tamd_stage_add(st, distance_max, nb, TAMD_IN, &a.distance_max);
+        tamd_stage_add(st, index, 2 * ni, TAMD_OUT, &a.index);
+        tamd_stage_add(st, depth, nb, TAMD_OUT, &a.depth);
+        tamd_stage_add(st, distance, nb, TAMD_OUT, &a.distance);
+        tamd_stage_add(st, n_steps, ni, TAMD_OUT, &a.n_steps);
+        tamd_stage_add(st, status, ni, TAMD_OUT, &a.status);
+        if (tamd_stage_open(st, space)) return TAMD_RAISE_DEVICE();
+        const int rc = stepper_resident(stepper, &advance_resident, &a);
+        stepper->last_rounds = 1;
+        if (rc != 0) return RAISE_ROUNDS(stepper, rc);
+        if (a.paged)
+                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "a tile left its stack while the call was made: try again");
+        if (tamd_stage_close(st)) return TAMD_RAISE_DEVICE();
+        return TURTLE_RETURN_SUCCESS;
+}
+
 int turtle_amd_stepper_rounds(const struct turtle_stepper * stepper) { return stepper->last_rounds; }
 
 enum turtle_return turtle_stepper_trace_stats(
