@@ -1822,6 +1822,24 @@ __device__ __forceinline__ int normal(const Geometry<MODE, MATH> & g, const doub
         return found;
 }
 
+/* ---- column depth along a step in an exponential medium ------------------------
+ * The arithmetic of turtle_stepper_advance_exp_n (include/turtle_amd.h states the loop), for a
+ * caller that steps rays inside its own kernel.  Over a step of length ds from altitude a0 to a1,
+ * in a medium of density rho0 * exp(-h / H), the altitude is taken as linear in the path: the
+ * density f metres into the step is c * exp(w * f), with
+ *     c = rho0 * exp(-a0 / H),   w = -((a1 - a0) / H) / ds        (uniform medium: c = rho0, w = 0).
+ * column_depth: the depth of the step's first f metres.  column_reach: its inverse, how far into
+ * the step the depth R lasts (NaN where the step never spends R: no comparison with it holds).
+ * Plain double-precision exp-family functions, whatever the arithmetic of the stepping. */
+__device__ __forceinline__ double column_depth(double c, double w, double f)
+{
+        return (w * f == 0.) ? c * f : c * expm1(w * f) / w;
+}
+__device__ __forceinline__ double column_reach(double c, double w, double R)
+{
+        return (w == 0.) ? R / c : log1p(R * w / c) / w;
+}
+
 /* ---- the step machine of Stepping::trip() below and of the library's k_walk ----
  * One sample per live lane and trip, at q = B + d * t: the origin itself (ST_INIT, the callers'
  * own business), a tentative step (ST_STEP: t = ds), or one halving of a crossing (ST_BISECT:

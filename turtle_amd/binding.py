@@ -865,13 +865,16 @@ class Stepper:
                     n_crossings=ncross, point=point, distance=distance, media=media)
 
     def advance(self, position, direction, density, budget, distance_max=None,
-                altitude_max=float("inf"), max_steps=1000000, want=("depth", "distance", "n_steps")):
+                altitude_max=float("inf"), max_steps=1000000, want=("depth", "distance", "n_steps"),
+                scale_height=None):
         """turtle_stepper_advance_n -> dict(position, index, depth, distance, n_steps, status): each
         ray stepped as traverse steps it until its column depth (the sum of density[medium] x
         path) reaches budget[r], its path reaches distance_max[r] (None: no limit), or the
         geometry stops it; `status` says which (ADVANCE_SPENT ... ADVANCE_MAX_STEPS).  `density`
-        has `media` elements.  The position advances in place (as in traverse)."""
-        sp = _space_of(position, direction, density, budget, distance_max)
+        has `media` elements.  The position advances in place (as in traverse).  With
+        `scale_height` (`media` elements, inf: uniform) the call is turtle_stepper_advance_exp_n:
+        the density of medium m at altitude h is density[m] exp(-h / scale_height[m])."""
+        sp = _space_of(position, direction, density, budget, distance_max, scale_height)
         pos = _as(position, sp).reshape(-1, 3)
         d = _as(direction, sp).reshape(-1, 3)
         n = pos.shape[0]
@@ -887,6 +890,16 @@ class Stepper:
         distance = _new((n,), sp, like=pos) if "distance" in want else None
         nsteps = _new((n,), sp, np.int32, like=pos) if "n_steps" in want else None
         status = _new((n,), sp, np.int32, like=pos)
+        if scale_height is not None:
+            sh = _as(scale_height, sp).reshape(-1)
+            if sh.shape[0] != self.media:
+                raise ValueError(f"scale_height has {sh.shape[0]} elements for {self.media} media")
+            _check(lib().turtle_stepper_advance_exp_n(self.h, C.c_long(n), _ptr(pos), _ptr(d), _ptr(rho), _ptr(sh),
+                                                      _ptr(b), _ptr(dmax), C.c_double(altitude_max),
+                                                      int(max_steps), _ptr(index), _ptr(depth), _ptr(distance),
+                                                      _ptr(nsteps), _ptr(status), sp))
+            return dict(position=pos, index=index, depth=depth, distance=distance, n_steps=nsteps,
+                        status=status)
         _check(lib().turtle_stepper_advance_n(self.h, C.c_long(n), _ptr(pos), _ptr(d), _ptr(rho), _ptr(b),
                                               _ptr(dmax), C.c_double(altitude_max), int(max_steps),
                                               _ptr(index), _ptr(depth), _ptr(distance), _ptr(nsteps),

@@ -2885,7 +2885,18 @@ __global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * 
  * while a crossing is halved it lies in the registers of the sample the ray stood
  * on, which is dead by then.  The tests after an event are traverse's in
  * traverse's order with the two budget tests between them; with B = inf and no M
- * they never fire: the bits of k_traverse. */
+ * they never fire: the bits of k_traverse.
+ *
+ * LAW (turtle_stepper_advance_exp_n with scale heights): the density of medium m at
+ * altitude h is density[m] * exp(-h / scale_height[m]), the altitude taken as linear
+ * in the path within a step.  A LAW lane keeps two values more: ih, the reciprocal of
+ * its medium's scale height (0: the medium is uniform), read with rho when the ray
+ * enters a medium; and a0, the altitude its step began at, for the time a crossing is
+ * halved (s_alt holds p0x then; for an accepted step a0 is still in s_alt at the
+ * event).  exp, expm1 and log1p run at events only, the plain double-precision
+ * functions in either arithmetic, and a lane whose medium is uniform branches past
+ * them: its bits are those of the instance without the law.  The step's depth and its
+ * inverse are turtle_amd_device.h's column_depth and column_reach. */
 struct AdvanceIO {
         const double * __restrict__ dir;
         const double * __restrict__ density;  /* [media] */
@@ -2898,10 +2909,17 @@ struct AdvanceIO {
         double ceiling;
         int max_steps;
 };
+struct AdvanceLawIO : AdvanceIO {
+        const double * __restrict__ scale_height; /* [media] */
+};
 
-template <int MODE, bool FAST>
+/* what a LAW lane keeps of its medium's scale height H: 1 / H, and 0 for the uniform H = HUGE_VAL */
+__device__ __forceinline__ double d_inverse_scale(double H) { return (H == HUGE_VAL) ? 0. : 1. / H; }
+
+template <int MODE, bool FAST, bool LAW = false>
 __global__ void __launch_bounds__(256) k_advance(tamd_view v, long n, double * __restrict__ pos,
-    int * __restrict__ index, AdvanceIO io, ull * __restrict__ stats, ull * __restrict__ queue)
+    int * __restrict__ index, std::conditional_t<LAW, AdvanceLawIO, AdvanceIO> io, ull * __restrict__ stats,
+    ull * __restrict__ queue)
 {
         RayQueue q;
         OneCtx ctx;
@@ -2915,6 +2933,7 @@ __global__ void __launch_bounds__(256) k_advance(tamd_view v, long n, double * _
         double bx = 0, by = 0, bz = 0, dx = 0, dy = 0, dz = 0;
         double X = 0, d = 0, B = 0, M = 0;
         double rho = 0; /* density[m]: read when the ray enters a medium, not at every step */
+        double ih = 0, a0 = 0; /* (LAW) 1 / scale_height[m], or 0: uniform; the altitude a halved step began at */
         double ds = 0;
         /* the sample the ray stands on -- and, while it halves a crossing (ds is set, the sample
          * no longer needed: an event replaces it), the position p0 its step began at */
@@ -2948,6 +2967,9 @@ __global__ void __launch_bounds__(256) k_advance(tamd_view v, long n, double * _
                                 m = s.m, k = s.k;
                                 s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
                                 if (m >= 0) rho = io.density[m];
+                                if constexpr (LAW) {
+                                        if (m >= 0) ih = d_inverse_scale(io.scale_height[m]);
+                                }
                                 state = ST_STEP;
                                 event = true;
                         } else {
@@ -2956,26 +2978,39 @@ __global__ void __launch_bounds__(256) k_advance(tamd_view v, long n, double * _
                                 const StepOutcome o = step_or_bisect(b, state, bx, by, bz, m, ds, t, qx, qy, qz, s);
                                 my_steps += stepping ? 1 : 0;
                                 event = o.accept | o.located;
+                                if constexpr (LAW) {
+                                        if (stepping & !o.accept) a0 = s_alt;
+                                }
                                 if (stepping & !o.accept) s_alt = ox, s_e0 = oy, s_e1 = oz; /* p0, kept for the halving */
                                 if (event) {
                                         const double p0x = o.accept ? ox : s_alt, p0y = o.accept ? oy : s_e0,
                                                      p0z = o.accept ? oz : s_e1;
                                         /* the step's full length, in the medium m it started in */
                                         const double len = o.located ? ds + b.ds1 : ds;
-                                        const double x = rho * len;
+                                        double x = rho * len;
+                                        double c = rho, w = 0.; /* the step's law: column_depth(c, w, f) */
+                                        if constexpr (LAW) {
+                                                if (ih != 0.) {
+                                                        const double h0 = o.accept ? s_alt : a0;
+                                                        const double h1 = o.accept ? s.alt : b.b_alt;
+                                                        c = rho * exp(-h0 * ih);
+                                                        w = -((h1 - h0) * ih) / len;
+                                                        x = column_depth(c, w, len);
+                                                }
+                                        }
                                         const bool spent = (X + x >= B), far = (d + len >= M);
                                         count++;
                                         if (spent | far) { /* the step is cut short, inside medium m */
                                                 double f = far ? M - d : len;
                                                 status = far ? TURTLE_AMD_ADVANCE_DISTANCE : TURTLE_AMD_ADVANCE_SPENT;
                                                 if (spent) {
-                                                        const double fs = (B - X) / rho;
+                                                        const double fs = LAW ? column_reach(c, w, B - X) : (B - X) / rho;
                                                         if (fs <= f) f = fs, status = TURTLE_AMD_ADVANCE_SPENT;
                                                 }
                                                 if (f > len) f = len; /* (a rounding guard) */
                                                 bx = p0x + dx * f, by = p0y + dy * f, bz = p0z + dz * f;
                                                 const bool by_depth = (status == TURTLE_AMD_ADVANCE_SPENT);
-                                                X = by_depth ? B : X + rho * f;
+                                                X = by_depth ? B : X + (LAW ? column_depth(c, w, f) : rho * f);
                                                 d = by_depth ? d + f : M;
                                         } else {
                                                 X += x, d += len;
@@ -2987,6 +3022,9 @@ __global__ void __launch_bounds__(256) k_advance(tamd_view v, long n, double * _
                                                         m = b.bm, k = b.bk;
                                                         s_alt = b.b_alt, s_e0 = b.b_e0, s_e1 = b.b_e1;
                                                         if (m >= 0) rho = io.density[m];
+                                                        if constexpr (LAW) {
+                                                                if (m >= 0) ih = d_inverse_scale(io.scale_height[m]);
+                                                        }
                                                 }
                                         }
                                         state = ST_STEP;
@@ -4353,10 +4391,11 @@ extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, cons
         });
 }
 
-/* A whole advance in one launch (k_advance): every tile resident, nothing listed */
+/* A whole advance in one launch (k_advance): every tile resident, nothing listed.  scale_height
+ * NULL: the instances without the law */
 extern "C" int tamd_k_advance(struct tamd_view view, long n, double * pos, const double * dir,
-    const double * density, const double * budget, const double * distance_max, double ceiling,
-    int max_steps, int * index, double * depth, double * distance, int * n_steps, int * status,
+    const double * density, const double * scale_height, const double * budget, const double * distance_max,
+    double ceiling, int max_steps, int * index, double * depth, double * distance, int * n_steps, int * status,
     unsigned long long * stats, unsigned long long * queue)
 {
         if (tamd_dev_init()) return 1;
@@ -4367,6 +4406,14 @@ extern "C" int tamd_k_advance(struct tamd_view view, long n, double * pos, const
         const bool strict = g_math_strict || !view.fast_ok;
         return with_mode(view.mode, [&](auto mode) {
                 return with_math(strict, [&](auto fast) {
+                        if (scale_height != nullptr) {
+                                AdvanceLawIO law;
+                                static_cast<AdvanceIO &>(law) = io;
+                                law.scale_height = scale_height;
+                                const auto kernel = k_advance<decltype(mode)::value, decltype(fast)::value, true>;
+                                return launch_blocks("k_advance", kernel, persistent_blocks(kernel, n), 0, view, n,
+                                    pos, index, law, stats, queue);
+                        }
                         const auto kernel = k_advance<decltype(mode)::value, decltype(fast)::value>;
                         return launch_blocks("k_advance", kernel, persistent_blocks(kernel, n), 0, view, n, pos,
                             index, io, stats, queue);

@@ -1450,14 +1450,14 @@ enum turtle_return turtle_stepper_crossings_n(struct turtle_stepper * stepper, l
             length, n_steps, n_crossings, &rec, space);
 }
 
-/* turtle_stepper_advance_n: resident tiles only (a cut needs the position its step began at, which
- * the generation kernels overwrite): one launch through stepper_resident, and sight_run's closing
- * sequence over a stage of its own. */
+/* turtle_stepper_advance_n and turtle_stepper_advance_exp_n (scale_height, or NULL): resident tiles
+ * only (a cut needs the position its step began at, which the generation kernels overwrite): one
+ * launch through stepper_resident, and sight_run's closing sequence over a stage of its own. */
 struct advance_args {
         struct tamd_stage stage;
         int paged; /* out: a tile was not resident when the tables were made current */
         long n;
-        void *pos, *dir, *density, *budget, *distance_max, *index, *depth, *distance, *n_steps, *status;
+        void *pos, *dir, *density, *scale_height, *budget, *distance_max, *index, *depth, *distance, *n_steps, *status;
         double ceiling;
         int max_steps;
 };
@@ -1467,17 +1467,17 @@ static int advance_resident(struct turtle_stepper * stepper, struct tamd_paging 
         struct advance_args * a = p;
         (void)pg, (void)round;
         if ((a->paged = stepper_is_paged(stepper))) return 0; /* (a tile another thread took meanwhile) */
-        return tamd_k_advance(stepper->view, a->n, a->pos, a->dir, a->density, a->budget, a->distance_max,
-            a->ceiling, a->max_steps, a->index, a->depth, a->distance, a->n_steps, a->status, stepper->d_stats,
+        return tamd_k_advance(stepper->view, a->n, a->pos, a->dir, a->density, a->scale_height, a->budget,
+            a->distance_max, a->ceiling, a->max_steps, a->index, a->depth, a->distance, a->n_steps, a->status, stepper->d_stats,
             stepper->d_stats + TAMD_STATS_QUEUE);
 }
 
-enum turtle_return turtle_stepper_advance_n(struct turtle_stepper * stepper, long n, double * position,
-    const double * direction, const double * density, const double * budget, const double * distance_max,
-    double altitude_max, int max_steps, int * index, double * depth, double * distance, int * n_steps,
-    int * status, int space)
+static enum turtle_return advance_n(const struct tamd_error * error, struct turtle_stepper * stepper, long n,
+    double * position, const double * direction, const double * density, const double * scale_height,
+    const double * budget, const double * distance_max, double altitude_max, int max_steps, int * index,
+    double * depth, double * distance, int * n_steps, int * status, int space)
 {
-        TAMD_ERROR_INIT(&turtle_stepper_advance_n);
+        struct tamd_error error_ = *error;
         if ((stepper == NULL) || (position == NULL) || (direction == NULL) || (density == NULL) ||
             (budget == NULL) || (index == NULL) || (status == NULL))
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
@@ -1496,6 +1496,7 @@ enum turtle_return turtle_stepper_advance_n(struct turtle_stepper * stepper, lon
         tamd_stage_add(st, position, 3 * nb, TAMD_INOUT, &a.pos);
         tamd_stage_add(st, direction, 3 * nb, TAMD_IN, &a.dir);
         tamd_stage_add(st, density, media * sizeof(double), TAMD_IN, &a.density);
+        tamd_stage_add(st, scale_height, media * sizeof(double), TAMD_IN, &a.scale_height);
         tamd_stage_add(st, budget, nb, TAMD_IN, &a.budget);
         tamd_stage_add(st, distance_max, nb, TAMD_IN, &a.distance_max);
         tamd_stage_add(st, index, 2 * ni, TAMD_OUT, &a.index);
@@ -1511,6 +1512,26 @@ enum turtle_return turtle_stepper_advance_n(struct turtle_stepper * stepper, lon
                 return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "a tile left its stack while the call was made: try again");
         if (tamd_stage_close(st)) return TAMD_RAISE_DEVICE();
         return TURTLE_RETURN_SUCCESS;
+}
+
+enum turtle_return turtle_stepper_advance_n(struct turtle_stepper * stepper, long n, double * position,
+    const double * direction, const double * density, const double * budget, const double * distance_max,
+    double altitude_max, int max_steps, int * index, double * depth, double * distance, int * n_steps,
+    int * status, int space)
+{
+        TAMD_ERROR_INIT(&turtle_stepper_advance_n);
+        return advance_n(&error_, stepper, n, position, direction, density, NULL, budget, distance_max,
+            altitude_max, max_steps, index, depth, distance, n_steps, status, space);
+}
+
+enum turtle_return turtle_stepper_advance_exp_n(struct turtle_stepper * stepper, long n, double * position,
+    const double * direction, const double * density, const double * scale_height, const double * budget,
+    const double * distance_max, double altitude_max, int max_steps, int * index, double * depth,
+    double * distance, int * n_steps, int * status, int space)
+{
+        TAMD_ERROR_INIT(&turtle_stepper_advance_exp_n);
+        return advance_n(&error_, stepper, n, position, direction, density, scale_height, budget, distance_max,
+            altitude_max, max_steps, index, depth, distance, n_steps, status, space);
 }
 
 int turtle_amd_stepper_rounds(const struct turtle_stepper * stepper) { return stepper->last_rounds; }
