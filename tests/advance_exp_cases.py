@@ -55,7 +55,7 @@ def _p(a):
 
 
 def check(geometry, position, direction, density, scale_height, budget, distance_max=None,
-          altitude_max=np.inf, max_steps=1000000, threads=None):
+          altitude_max=np.inf, max_steps=1000000, threads=None, slope=0.4, resolution=1e-2):
     """The definition's loop over the CPU restatement -> dict(OUTPUTS)"""
     pos = np.array(position, dtype=np.float64, order="C").reshape(-1, 3)
     d = np.ascontiguousarray(direction, dtype=np.float64).reshape(-1, 3)
@@ -69,7 +69,7 @@ def check(geometry, position, direction, density, scale_height, budget, distance
     out = dict(position=pos, index=np.empty((n, 2), dtype=np.int32), depth=np.empty(n), distance=np.empty(n),
                n_steps=np.empty(n, dtype=np.int32), status=np.empty(n, dtype=np.int32))
     threads = threads or min(64, os.cpu_count() or 1)
-    checker().advance_exp_loop(geometry.ref, C.c_double(0.4), C.c_double(1e-2), C.c_long(n), _p(pos), _p(d),
+    checker().advance_exp_loop(geometry.ref, C.c_double(slope), C.c_double(resolution), C.c_long(n), _p(pos), _p(d),
                                _p(rho), _p(sh), _p(b), _p(dm), C.c_double(altitude_max), C.c_int(max_steps),
                                _p(out["index"]), _p(out["depth"]), _p(out["distance"]), _p(out["n_steps"]),
                                _p(out["status"]), C.c_int(threads))

@@ -38,7 +38,8 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def check(geometry, position, direction, altitude_max=np.inf, max_steps=1000000, threads=None):
+def check(geometry, position, direction, altitude_max=np.inf, max_steps=1000000, threads=None, slope=0.4,
+          resolution=1e-2):
     """The loop over the CPU restatement, twice (the counts, then every crossing): traverse's
     outputs (index, length [media][n], n_steps, n_crossings, position) and the crossings, ragged:
     ray r's are rows offset[r] .. offset[r + 1] - 1 of point [rows][3], distance [rows] and
@@ -55,7 +56,7 @@ def check(geometry, position, direction, altitude_max=np.inf, max_steps=1000000,
                    n_steps=np.empty(n, dtype=np.int32), n_crossings=np.empty(n, dtype=np.int32))
         rows = 0 if offset is None else int(offset[-1])
         rec = dict(point=np.zeros((rows, 3)), distance=np.zeros(rows), media=np.zeros((rows, 2), np.int32))
-        checker().crossings_loop(geometry.ref, C.c_double(0.4), C.c_double(1e-2), C.c_long(n), _p(pos),
+        checker().crossings_loop(geometry.ref, C.c_double(slope), C.c_double(resolution), C.c_long(n), _p(pos),
                                  _p(d), C.c_double(altitude_max), C.c_int(max_steps), _p(out["index"]),
                                  _p(out["length"]), _p(out["n_steps"]), _p(out["n_crossings"]),
                                  _p(offset), _p(rec["point"]), _p(rec["distance"]), _p(rec["media"]),

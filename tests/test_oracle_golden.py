@@ -303,3 +303,29 @@ def test_g14_composite_geometries(golden):
         o, rows = geo.step(start), g[k + "step"]
         assert eq(o["latitude"], rows[:, 0]) and eq(o["longitude"], rows[:, 1]) and eq(o["altitude"], rows[:, 2])
         assert eq(o["elevation"], rows[:, 3:5]) and eq(o["index"], rows[:, 5:7].astype(np.int32)), k
+
+
+def test_g15_slope_and_resolution(golden):
+    """Traces at slope and resolution other than the defaults (tests/params_cases.py: the reference
+    example's slope 1, slope 2 and 0.1, resolutions of 1e-3, 0.25 and 1 m) over the smooth and the
+    rough tile: the restatement against the reference (params.npz), bit for bit"""
+    import params_cases as PC
+    import traverse_cases as TC
+    g = golden("params")
+    assert T.sha(TC.nodes("rough")) == str(g["rough_nodes_sha"])
+    for case in PC.CASES:
+        geo = TC.oracle_geometry(case)
+        for recipe in PC.RECIPES:
+            pos, d = g[f"{case}_{recipe}_position"], g[f"{case}_{recipe}_direction"]
+            if recipe != "c2":          # the stored rays are the recipe's
+                lat, lon, height, az, el = PC.draws(case, recipe)
+                assert eq(geo.position(lat, lon, height)[0], pos)
+                assert eq(O.ecef_from_horizontal(lat, lon, az, el), d)
+            for name in PC.settings(case):
+                slope, resolution = PC.SETTINGS[name]
+                k = f"{case}_{recipe}_{name}_"
+                t = geo.trace(pos, d, max_steps=PC.MAX_STEPS, slope=slope, resolution=resolution, threads=4)
+                assert eq(t["index"], g[k + "index"].astype(np.int32)), k
+                assert eq(t["n_steps"], g[k + "n_steps"]) and eq(t["length"], g[k + "length"]), k
+                assert (t["n_steps"] < PC.MAX_STEPS).all(), k
+    assert "rough_c2_steep_index" not in g

@@ -94,3 +94,30 @@ def test_walks_equal_bit_for_bit_and_the_client_memo_quirk(golden):
     # memo outlives the ray that set it -- the NEXT ray of that client starts "outside" and takes none
     assert (locked["n_steps"] <= taken).all()
     assert (locked["n_steps"][differs] < taken[differs]).any() and (locked["n_steps"][differs] == 0).any()
+
+
+def test_slope_and_resolution_against_the_compiled_reference(golden, tmp_path):
+    """Where the reference's build is present (oracle/_ref): it reproduces params.npz now, and the
+    restatement agrees with it bit for bit at every setting of tests/params_cases.py -- end positions
+    included, which the fixture does not store"""
+    from oracle import ref_ffi as R
+    if not R.driver_available():
+        pytest.skip("oracle/_ref is not built here")
+    import params_cases as PC
+    import traverse_cases as TC
+    g = golden("params")
+    for case in PC.CASES:
+        tile = TC.write_tile(tmp_path / case, case)
+        geo = TC.oracle_geometry(case)
+        for recipe in PC.RECIPES:
+            pos, d = g[f"{case}_{recipe}_position"], g[f"{case}_{recipe}_direction"]
+            for name in PC.settings(case):
+                slope, resolution = PC.SETTINGS[name]
+                k = f"{case}_{recipe}_{name}_"
+                theirs = R.trace_map(tile, pos, d, local_range=0.0, slope=slope, resolution=resolution,
+                                     max_steps=PC.MAX_STEPS, threads=4)
+                ours = geo.trace(pos, d, max_steps=PC.MAX_STEPS, slope=slope, resolution=resolution, threads=4)
+                assert np.array_equal(theirs["index"], g[k + "index"].astype(np.int32)), k
+                assert np.array_equal(theirs["length"], g[k + "length"]), k
+                for key in ("index", "n_steps", "length", "position"):
+                    assert np.array_equal(theirs[key], ours[key]), (k, key)

@@ -71,7 +71,8 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def check(geometry, position, direction, altitude_max=np.inf, max_steps=1000000, threads=None):
+def check(geometry, position, direction, altitude_max=np.inf, max_steps=1000000, threads=None, slope=0.4,
+          resolution=1e-2):
     """The loop over the CPU restatement: index, length [media][n], n_steps, n_crossings, position"""
     pos = np.array(position, dtype=np.float64, order="C").reshape(-1, 3)
     d = np.ascontiguousarray(direction, dtype=np.float64).reshape(-1, 3)
@@ -80,7 +81,7 @@ def check(geometry, position, direction, altitude_max=np.inf, max_steps=1000000,
     out = dict(index=np.empty((n, 2), dtype=np.int32), length=np.zeros((media, n)),
                n_steps=np.empty(n, dtype=np.int32), n_crossings=np.empty(n, dtype=np.int32))
     threads = threads or min(64, os.cpu_count() or 1)
-    checker().traverse_loop(geometry.ref, C.c_double(0.4), C.c_double(1e-2), C.c_long(n), _p(pos), _p(d),
+    checker().traverse_loop(geometry.ref, C.c_double(slope), C.c_double(resolution), C.c_long(n), _p(pos), _p(d),
                             C.c_double(altitude_max), C.c_int(max_steps), _p(out["index"]),
                             _p(out["length"]), _p(out["n_steps"]), _p(out["n_crossings"]),
                             C.c_int(threads))

@@ -3529,6 +3529,16 @@ __global__ void __launch_bounds__(256) k_nodes(const uint16_t * __restrict__ nod
 #define g_cus (g_ctx.cus)
 #define g_math_strict (g_ctx.math_strict)
 
+/* Which arithmetic a stepping call runs in.  FAST takes its samples from closed forms and lines that
+ * are a few 1e-9 m off the exact transform (kLineTau0): a stepper whose minimum step is below the
+ * 1e-8 m of the bisection's bracket asks for steps finer than that noise -- a ray that creeps along
+ * the ground then crosses it tens of steps earlier or later than the reference's, or not before
+ * max_steps -- and is served by the STRICT kernels whatever the mode (a NaN resolution too). */
+static bool strict_math(const tamd_view & view)
+{
+        return g_math_strict || !view.fast_ok || !(view.resolution >= 1E-08);
+}
+
 #ifdef TRACE_POOL_STATS
 extern "C" int tamd_dev_pool_stats(unsigned long long * out, int reset)
 {
@@ -3726,7 +3736,7 @@ static int run_step(struct tamd_view view, long n, double * pos, const double * 
     double * lat, double * lon, double * alt, double * elev, double * step, int * index,
     int flags, CrossList cross, Paging pg, ull * stats, StepWalk walk)
 {
-        const bool strict = g_math_strict || !view.fast_ok;
+        const bool strict = strict_math(view);
         return with_mode(view.mode, [&](auto mode) {
                 constexpr int MODE = decltype(mode)::value;
                 /* (the fast step of one map / one stack is a kernel of its own: see k_step_fast) */
@@ -4227,7 +4237,7 @@ static int run_trace(struct tamd_view view, long n, TraceRays rays, int max_step
 {
         const bool again = (pg.ids != nullptr);
         if (again) flags |= TRACE_CARRY_MEDIUM;
-        const bool strict = g_math_strict || !view.fast_ok;
+        const bool strict = strict_math(view);
         const bool listed = (room != nullptr) && (rays.length != nullptr) && (rays.n_steps != nullptr);
         tamd_trace_room at;
         tamd_trace_room_layout(&at, n);
@@ -4352,7 +4362,7 @@ extern "C" int tamd_k_walk(struct tamd_view view, long n, double * pos, double *
         HIP_TRY(hipMemsetAsync(queue, 0, sizeof(ull), g_stream));
         if (n <= 0) return 0;
         const WalkIO io = { seed, first, first_step, n_steps };
-        const bool strict = g_math_strict || !view.fast_ok;
+        const bool strict = strict_math(view);
         return with_mode(view.mode, [&](auto mode) {
                 return with_math(strict, [&](auto fast) {
                         const auto kernel = k_walk<decltype(mode)::value, decltype(fast)::value>;
@@ -4382,7 +4392,7 @@ extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, cons
         if (zero_words(stats, 4, queue, 1)) return 1;
         if (n <= 0) return 0;
         const TraverseIO io = { dir, length, n_steps, n_cross, ceiling, max_steps };
-        const bool strict = g_math_strict || !view.fast_ok;
+        const bool strict = strict_math(view);
         return with_mode(view.mode, [&](auto mode) {
                 constexpr int MODE = decltype(mode)::value;
                 if (rec != nullptr)
@@ -4403,7 +4413,7 @@ extern "C" int tamd_k_advance(struct tamd_view view, long n, double * pos, const
         if (n <= 0) return 0;
         const AdvanceIO io = { dir, density, budget, distance_max, depth, distance, n_steps, status, ceiling,
                 max_steps };
-        const bool strict = g_math_strict || !view.fast_ok;
+        const bool strict = strict_math(view);
         return with_mode(view.mode, [&](auto mode) {
                 return with_math(strict, [&](auto fast) {
                         if (scale_height != nullptr) {
