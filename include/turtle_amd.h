@@ -1062,7 +1062,111 @@ TURTLE_API enum turtle_return turtle_stepper_advance_exp_n(
     double * depth /* [n] or NULL */, double * distance /* [n] or NULL */,
     int * n_steps /* [n] or NULL */, int * status /* [n], mandatory */, int space);
 
-/* Totals of the LAST trace_n, scatter_n, traverse_n, crossings_n, advance_n or advance_exp_n call on this stepper,
+/* A box of voxels with straight edges in ECEF, each voxel one density: the rock of a volcano, an
+ * ore body, an aquifer under a hill.  A voxel (i0, i1, i2) spans origin + sum over a of
+ * axis[a] * [i_a, i_a + 1] * size[a].  The axes are taken as given and are expected to be
+ * orthonormal (turtle_amd_grid_enu makes them so); they are not checked. */
+struct turtle_amd_grid {
+        double origin[3];       /* ECEF of the corner of voxel (0, 0, 0) that every axis leaves from */
+        double axis[3][3];      /* unit vectors of the grid's three directions, in ECEF */
+        double size[3];         /* a voxel's edge along each axis, metres */
+        int n[3];               /* voxels along each axis */
+        int medium;             /* the medium the grid describes (0: under the first layer's top) */
+        const double * density; /* [n[2]][n[1]][n[0]], axis 0 fastest; lies in the call's `space` */
+};
+
+/* origin and axis of a box whose axes are east, north, up at (latitude, longitude) [the frame of
+ * turtle_ecef_from_horizontal], its origin `east0`, `north0`, `up0` metres from the point
+ * (latitude, longitude, height) along them.  Host arithmetic; fills grid->origin and grid->axis only. */
+TURTLE_API void turtle_amd_grid_enu(struct turtle_amd_grid * grid, double latitude, double longitude,
+    double height, double east0, double north0, double up0);
+
+/* turtle_stepper_advance_n through rock whose density varies in three dimensions: inside the box
+ * `grid` the density of medium grid->medium is the voxel's; outside the box that medium has
+ * density[grid->medium], and every other medium is turtle_stepper_advance_n's.  A ray is a straight
+ * line in ECEF and so are the box's edges: the depth of a step is an exact sum over the voxels it
+ * meets, not a quadrature.  The struct itself is read on the host in both spaces; only
+ * grid->density follows `space` (HOST: staged to the device for the call; DEVICE: read where it
+ * lies).  For each ray r, exactly, turtle_stepper_advance_n's loop with its tests in its order; one
+ * walk a step takes the place of density[m] * ds and of the cut:
+ *
+ *     turtle_stepper_step(s, pos, NULL, NULL, NULL, &alt, NULL, NULL, idx);  X = 0; d = 0; steps = 0;
+ *     for (;;) {
+ *             if (idx[0] < 0)            { status = LEFT; break; }
+ *             if (!(X < B))              { status = SPENT; break; }
+ *             if (!(d < M))              { status = DISTANCE; break; }
+ *             if (!(alt < altitude_max)) { status = CEILING; break; }
+ *             if (steps >= max_steps)    { status = MAX_STEPS; break; }
+ *             m = idx[0]; k = idx[1]; p0 = pos;
+ *             turtle_stepper_step(s, pos, dir, NULL, NULL, &alt, NULL, &ds, idx);
+ *             far = (d + ds >= M);  L = far ? M - d : ds;  if (L > ds) L = ds;
+ *             (x, f, stopped) = grid_depth(grid, density[m], m, p0, dir, L, B - X);
+ *             if (stopped) { pos = p0 + dir * f; X = B;  d += f; steps++; idx = {m, k}; status = SPENT;    break; }
+ *             if (far)     { pos = p0 + dir * L; X += x; d = M;  steps++; idx = {m, k}; status = DISTANCE; break; }
+ *             X += x; d += ds; steps++;
+ *     }
+ *     index[r] = idx; depth[r] = X; distance[r] = d; n_steps[r] = steps; status[r] = status;
+ *
+ * grid_depth(G, rho_out, m, p0, dir, L, R) goes through the pieces of [0, L] in order and adds
+ * rho * (b - a) for each piece (a, b, rho) to a running sum acc, starting from 0.  A piece with
+ * x = rho * (b - a) > 0 and acc + x >= R stops the walk at f = a + (R - acc) / rho (stopped): a
+ * piece of density 0 never stops a ray and never divides.  Otherwise the walk returns x = acc,
+ * f = L, not stopped.  The pieces:
+ *
+ *     if (G == NULL || m != G->medium): one piece (0, L, rho_out).
+ *     s[a] = axis[a][0]*(p0[0]-origin[0]) + axis[a][1]*(p0[1]-origin[1]) + axis[a][2]*(p0[2]-origin[2]);
+ *     t[a] = axis[a][0]*dir[0] + axis[a][1]*dir[1] + axis[a][2]*dir[2];                  (a = 0, 1, 2)
+ *     f0 = 0; f1 = L; hit = 1;                                                           (the slab test)
+ *     for a: E = n[a] * size[a];
+ *            if (t[a] == 0) { if (!(s[a] >= 0 && s[a] < E)) hit = 0; }
+ *            else { u = (0 - s[a]) / t[a]; v = (E - s[a]) / t[a]; if (u > v) swap(u, v);
+ *                   if (u > f0) f0 = u;  if (v < f1) f1 = v; }
+ *     f = 0;
+ *     if (hit && f0 < f1) {
+ *             piece (0, f0, rho_out);
+ *             for a: i[a] = clamp((int)floor((s[a] + f0 * t[a]) / size[a]), 0, n[a] - 1);
+ *                    next[a] = (t[a] == 0) ? HUGE_VAL : ((i[a] + (t[a] > 0)) * size[a] - s[a]) / t[a];
+ *             f = f0;
+ *             for (;;) {
+ *                     a = the axis of the least next[] (ties: the lowest a);
+ *                     g = min(next[a], f1);  if (g < f) g = f;                           (no piece is negative)
+ *                     piece (f, g, G->density[((long)i[2] * n[1] + i[1]) * n[0] + i[0]]);
+ *                     f = g;
+ *                     if (!(next[a] < f1)) break;
+ *                     i[a] += (t[a] > 0) ? 1 : -1;  if (i[a] < 0 || i[a] >= n[a]) break;
+ *                     next[a] = ((i[a] + (t[a] > 0)) * size[a] - s[a]) / t[a];           (from the index: nothing accumulates)
+ *             }
+ *     }
+ *     piece (f, L, rho_out);                                  (what lies past the box, or all of it)
+ *
+ * What follows from it, and is tested:
+ *  - grid = NULL is turtle_stepper_advance_n, bit for bit (the same kernel instance runs); error
+ *    messages carry this call's name;
+ *  - a SPENT ray has depth == budget and a DISTANCE ray distance == distance_max, to the bit;
+ *  - status, position and n_steps of a ray that no cut stopped are turtle_stepper_traverse_n's bits;
+ *  - a grid whose voxels all hold density[medium] agrees with turtle_stepper_advance_n to rounding
+ *    (one rounding a piece met), not to the bit: the sum is taken piece by piece;
+ *  - a voxel of density 0 (a void) spends nothing; where rock is void the place a budget ends is
+ *    discontinuous in the budget;
+ *  - densities are not checked.
+ * The walk is turtle_amd_device.h's grid_depth, for callers that step rays in their own kernel.
+ * BAD_ADDRESS as turtle_stepper_advance_n, and grid != NULL with grid->density == NULL.
+ * DOMAIN_ERROR as turtle_stepper_advance_n, and: an n[a] < 1, a size[a] that is not finite and
+ * > 0, n[0] * n[1] * n[2] beyond an int, medium outside [0, media).  All of them before a device is
+ * touched: nothing changes.  Everything else -- statuses, optional outputs, resident tiles only
+ * (paged stacks are refused), turtle_amd_stepper_rounds (1), turtle_stepper_trace_stats, spaces --
+ * is turtle_stepper_advance_n's.  Not offered: a grid together with scale heights, more than one
+ * grid, densities interpolated between voxel centres. */
+TURTLE_API enum turtle_return turtle_stepper_advance_grid_n(
+    struct turtle_stepper * stepper, long n, double * position /* [n][3], in / out */,
+    const double * direction /* [n][3] */, const double * density /* [media] */,
+    const struct turtle_amd_grid * grid /* host memory, or NULL */,
+    const double * budget /* [n] */, const double * distance_max /* [n] or NULL */,
+    double altitude_max, int max_steps, int * index /* [n][2], out */,
+    double * depth /* [n] or NULL */, double * distance /* [n] or NULL */,
+    int * n_steps /* [n] or NULL */, int * status /* [n], mandatory */, int space);
+
+/* Totals of the LAST trace_n, scatter_n, traverse_n, crossings_n, advance_n, advance_exp_n or advance_grid_n call on this stepper,
  * accumulated on the device: stats[0] rays, [1] steps, [2] samples (transform +
  * layer lookup; the same from run to run), [3] rays that stopped at max_steps.
  * Synchronises the stream. */

@@ -168,6 +168,21 @@ __attribute__((unused)) static inline int turtle_amd_view_ok(const struct turtle
         return (view->version == TURTLE_AMD_VIEW_VERSION) && (view->size == (int)sizeof(struct turtle_amd_view));
 }
 
+/* struct turtle_amd_grid (turtle_amd.h) as a kernel reads it: a POD, passed BY VALUE like the view
+ * (the scalars then sit in scalar registers); `density` is a DEVICE pointer to n[2] x n[1] x n[0]
+ * voxels, axis 0 fastest.  The argument of turtle_amd_device::grid_depth below. */
+struct turtle_amd_grid_view {
+        double origin[3];
+        double axis[3][3];
+        double size[3];
+        int n[3];
+        int medium;
+        const double * density;
+};
+#ifdef __cplusplus
+typedef struct turtle_amd_grid_view turtle_amd_grid_view;
+#endif
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 
@@ -1838,6 +1853,106 @@ __device__ __forceinline__ double column_depth(double c, double w, double f)
 __device__ __forceinline__ double column_reach(double c, double w, double R)
 {
         return (w == 0.) ? R / c : log1p(R * w / c) / w;
+}
+
+/* ---- column depth along a step through a density grid --------------------------
+ * The walk of turtle_stepper_advance_grid_n (include/turtle_amd.h states it piece by piece), for a
+ * caller that steps rays inside its own kernel: the depth of the first L metres of the straight
+ * line p0 + dir * f, begun in medium m where the density is rho_out outside the box G and the
+ * voxel's inside it, stopped where the depth reaches R.  -> x: the depth of [0, L] (not stopped);
+ * f: where the walk ended (L, or the point where R was reached); stopped.  A voxel of density 0
+ * never stops the walk and nothing divides by it.  The line is straight in ECEF and so are the
+ * box's axes: the sum is exact, one term a voxel met.  The axes' state (s, t, the index, the next
+ * face) is kept in named registers and picked by selects, never by a runtime index: nothing goes
+ * to scratch.  A face's distance is computed from the voxel's index each time: nothing accumulates.
+ * The voxel index is clamped on entry and tested at every move: no load leaves the grid. */
+struct GridDepth {
+        double x, f;
+        bool stopped;
+};
+
+__device__ __forceinline__ GridDepth grid_depth(const turtle_amd_grid_view & G, double rho_out, int m,
+    double p0x, double p0y, double p0z, double dx, double dy, double dz, double L, double R)
+{
+        GridDepth out = { 0., L, false };
+        double acc = 0.;
+        /* one piece (a, b, rho) of [0, L]: true where it stops the walk */
+        const auto piece = [&](double a, double b, double rho) {
+                const double x = rho * (b - a);
+                if ((x > 0.) && (acc + x >= R)) {
+                        out.f = a + (R - acc) / rho, out.stopped = true;
+                        return true;
+                }
+                acc += x;
+                return false;
+        };
+        double f = 0.;
+        if (m == G.medium) {
+                const double rx = p0x - G.origin[0], ry = p0y - G.origin[1], rz = p0z - G.origin[2];
+                const double s0 = G.axis[0][0] * rx + G.axis[0][1] * ry + G.axis[0][2] * rz;
+                const double s1 = G.axis[1][0] * rx + G.axis[1][1] * ry + G.axis[1][2] * rz;
+                const double s2 = G.axis[2][0] * rx + G.axis[2][1] * ry + G.axis[2][2] * rz;
+                const double t0 = G.axis[0][0] * dx + G.axis[0][1] * dy + G.axis[0][2] * dz;
+                const double t1 = G.axis[1][0] * dx + G.axis[1][1] * dy + G.axis[1][2] * dz;
+                const double t2 = G.axis[2][0] * dx + G.axis[2][1] * dy + G.axis[2][2] * dz;
+                /* the slab test: [f0, f1] of [0, L] lies in the box */
+                double f0 = 0., f1 = L;
+                bool hit = true;
+                const auto slab = [&](double s, double t, int n, double size) {
+                        const double E = n * size;
+                        if (t == 0.) {
+                                if (!((s >= 0.) && (s < E))) hit = false;
+                        } else {
+                                double u = (0. - s) / t, v = (E - s) / t;
+                                if (u > v) {
+                                        const double swap = u;
+                                        u = v, v = swap;
+                                }
+                                if (u > f0) f0 = u;
+                                if (v < f1) f1 = v;
+                        }
+                };
+                slab(s0, t0, G.n[0], G.size[0]);
+                slab(s1, t1, G.n[1], G.size[1]);
+                slab(s2, t2, G.n[2], G.size[2]);
+                if (hit && (f0 < f1)) {
+                        if (piece(0., f0, rho_out)) return out;
+                        const auto enter = [&](double s, double t, int n, double size) {
+                                const double c = floor((s + f0 * t) / size);
+                                return (c > 0.) ? ((c < n - 1) ? (int)c : n - 1) : 0; /* (NaN: 0) */
+                        };
+                        const auto face = [](int i, double s, double t, double size) {
+                                return (t == 0.) ? HUGE_VAL : ((i + ((t > 0.) ? 1 : 0)) * size - s) / t;
+                        };
+                        int i0 = enter(s0, t0, G.n[0], G.size[0]), i1 = enter(s1, t1, G.n[1], G.size[1]),
+                            i2 = enter(s2, t2, G.n[2], G.size[2]);
+                        double n0 = face(i0, s0, t0, G.size[0]), n1 = face(i1, s1, t1, G.size[1]),
+                               n2 = face(i2, s2, t2, G.size[2]);
+                        f = f0;
+                        for (;;) {
+                                /* the axis of the nearest face (ties: the lowest) */
+                                const int a = ((n0 <= n1) && (n0 <= n2)) ? 0 : ((n1 <= n2) ? 1 : 2);
+                                const double na = (a == 0) ? n0 : ((a == 1) ? n1 : n2);
+                                double g = (na < f1) ? na : f1;
+                                if (g < f) g = f; /* (no piece is negative) */
+                                if (piece(f, g, G.density[((long)i2 * G.n[1] + i1) * G.n[0] + i0])) return out;
+                                f = g;
+                                if (!(na < f1)) break;
+                                const double ta = (a == 0) ? t0 : ((a == 1) ? t1 : t2);
+                                const double sa = (a == 0) ? s0 : ((a == 1) ? s1 : s2);
+                                const double za = (a == 0) ? G.size[0] : ((a == 1) ? G.size[1] : G.size[2]);
+                                const int ca = (a == 0) ? G.n[0] : ((a == 1) ? G.n[1] : G.n[2]);
+                                const int ia = ((a == 0) ? i0 : ((a == 1) ? i1 : i2)) + ((ta > 0.) ? 1 : -1);
+                                if ((ia < 0) || (ia >= ca)) break;
+                                const double nn = face(ia, sa, ta, za);
+                                i0 = (a == 0) ? ia : i0, i1 = (a == 1) ? ia : i1, i2 = (a == 2) ? ia : i2;
+                                n0 = (a == 0) ? nn : n0, n1 = (a == 1) ? nn : n1, n2 = (a == 2) ? nn : n2;
+                        }
+                }
+        }
+        piece(f, L, rho_out); /* what lies past the box, or all of it */
+        out.x = acc;
+        return out;
 }
 
 /* ---- the step machine of Stepping::trip() below and of the library's k_walk ----

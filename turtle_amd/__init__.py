@@ -10,7 +10,7 @@ if the library is missing or no gfx950 device is usable, calls fail loudly.
 from . import synth  # noqa: F401
 from .binding import (  # noqa: F401
     ADVANCE_CEILING, ADVANCE_DISTANCE, ADVANCE_LEFT, ADVANCE_MAX_STEPS, ADVANCE_SPENT,
-    CLEARANCE_PAIRED, DEVICE, HOST, STEP_RESUME, Map, Projection, Stack, Stepper, TurtleError, build, device_count,
+    CLEARANCE_PAIRED, DEVICE, Grid, HOST, STEP_RESUME, Map, Projection, Stack, Stepper, TurtleError, build, device_count,
     compute_units, ecef_from_geodetic, ecef_from_horizontal, ecef_to_geodetic,
     ecef_to_horizontal, get_math, isotropic, lib, philox, library_path, set_math, set_scalar, get_scalar, set_stream, set_in_flight, get_in_flight, synchronize,
     tally,

@@ -305,6 +305,51 @@ def scalar_ecef_from_geodetic(latitude, longitude, elevation):
 
 # ---- projections ---------------------------------------------------------------
 
+class _Grid(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("axis", (C.c_double * 3) * 3), ("size", C.c_double * 3),
+                ("n", C.c_int * 3), ("medium", C.c_int), ("density", C.c_void_p)]
+
+
+class Grid:
+    """struct turtle_amd_grid: a box of voxels with straight edges in ECEF, each voxel one density.
+    `origin` (3) is the ECEF corner of voxel (0, 0, 0), `axis` (3, 3) the unit vectors of the three
+    directions (expected orthonormal), `size` (3) a voxel's edges in metres, `density` an array
+    [n2][n1][n0] (axis 0 fastest), numpy or torch, and `medium` the medium the grid describes."""
+
+    def __init__(self, origin, axis, size, density, medium=0):
+        self.origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        self.axis = np.ascontiguousarray(axis, dtype=np.float64).reshape(3, 3)
+        self.size = np.ascontiguousarray(size, dtype=np.float64).reshape(3)
+        if not _is_torch(density):
+            density = np.asarray(density, dtype=np.float64)
+        if len(density.shape) != 3:
+            raise ValueError("density is an array [n2][n1][n0]")
+        self.density = density
+        self.n = tuple(int(v) for v in density.shape[::-1])
+        self.medium = int(medium)
+
+    @classmethod
+    def enu(cls, latitude, longitude, height, size, density, offset=(0, 0, 0), medium=0):
+        """turtle_amd_grid_enu: the box's axes east, north and up at (latitude, longitude), its
+        origin `offset` metres (east, north, up) from the point (latitude, longitude, height)"""
+        g = _Grid()
+        lib().turtle_amd_grid_enu(C.byref(g), C.c_double(latitude), C.c_double(longitude), C.c_double(height),
+                                  C.c_double(offset[0]), C.c_double(offset[1]), C.c_double(offset[2]))
+        _check(0)
+        return cls(np.array(g.origin), np.array([list(row) for row in g.axis]), size, density, medium)
+
+    def _struct(self, voxels):
+        g = _Grid()
+        g.origin[:] = self.origin.tolist()
+        for a in range(3):
+            g.axis[a][:] = self.axis[a].tolist()
+        g.size[:] = self.size.tolist()
+        g.n[:] = self.n
+        g.medium = self.medium
+        g.density = _ptr(voxels).value if voxels is not None else None
+        return g
+
+
 class Projection:
     """struct turtle_projection handle ("Lambert 93", "UTM 31N", ...)."""
 
@@ -866,15 +911,20 @@ class Stepper:
 
     def advance(self, position, direction, density, budget, distance_max=None,
                 altitude_max=float("inf"), max_steps=1000000, want=("depth", "distance", "n_steps"),
-                scale_height=None):
+                scale_height=None, grid=None):
         """turtle_stepper_advance_n -> dict(position, index, depth, distance, n_steps, status): each
         ray stepped as traverse steps it until its column depth (the sum of density[medium] x
         path) reaches budget[r], its path reaches distance_max[r] (None: no limit), or the
         geometry stops it; `status` says which (ADVANCE_SPENT ... ADVANCE_MAX_STEPS).  `density`
         has `media` elements.  The position advances in place (as in traverse).  With
         `scale_height` (`media` elements, inf: uniform) the call is turtle_stepper_advance_exp_n:
-        the density of medium m at altitude h is density[m] exp(-h / scale_height[m])."""
-        sp = _space_of(position, direction, density, budget, distance_max, scale_height)
+        the density of medium m at altitude h is density[m] exp(-h / scale_height[m]).  With `grid`
+        (a Grid) it is turtle_stepper_advance_grid_n: inside the box the density of grid.medium is
+        the voxel's; not together with `scale_height`."""
+        if grid is not None and scale_height is not None:
+            raise ValueError("a grid together with scale heights is not offered")
+        sp = _space_of(position, direction, density, budget, distance_max, scale_height,
+                       None if grid is None else grid.density)
         pos = _as(position, sp).reshape(-1, 3)
         d = _as(direction, sp).reshape(-1, 3)
         n = pos.shape[0]
@@ -898,6 +948,15 @@ class Stepper:
                                                       _ptr(b), _ptr(dmax), C.c_double(altitude_max),
                                                       int(max_steps), _ptr(index), _ptr(depth), _ptr(distance),
                                                       _ptr(nsteps), _ptr(status), sp))
+            return dict(position=pos, index=index, depth=depth, distance=distance, n_steps=nsteps,
+                        status=status)
+        if grid is not None:
+            voxels = _as(grid.density, sp)
+            g = grid._struct(voxels)
+            _check(lib().turtle_stepper_advance_grid_n(self.h, C.c_long(n), _ptr(pos), _ptr(d), _ptr(rho), C.byref(g),
+                                                       _ptr(b), _ptr(dmax), C.c_double(altitude_max),
+                                                       int(max_steps), _ptr(index), _ptr(depth), _ptr(distance),
+                                                       _ptr(nsteps), _ptr(status), sp))
             return dict(position=pos, index=index, depth=depth, distance=distance, n_steps=nsteps,
                         status=status)
         _check(lib().turtle_stepper_advance_n(self.h, C.c_long(n), _ptr(pos), _ptr(d), _ptr(rho), _ptr(b),

@@ -2896,7 +2896,18 @@ __global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * 
  * event).  exp, expm1 and log1p run at events only, the plain double-precision
  * functions in either arithmetic, and a lane whose medium is uniform branches past
  * them: its bits are those of the instance without the law.  The step's depth and its
- * inverse are turtle_amd_device.h's column_depth and column_reach. */
+ * inverse are turtle_amd_device.h's column_depth and column_reach.
+ *
+ * GRID (turtle_stepper_advance_grid_n): inside a box of voxels the density of ONE
+ * medium is the voxel's.  At an event a lane whose medium is the grid's walks the
+ * step's segment p0 + dir * [0, L] voxel by voxel (turtle_amd_device.h's grid_depth:
+ * the one copy of the arithmetic), L being the step's length or what the distance
+ * limit leaves of it; the walk itself stops where the budget runs out, so the far
+ * cut and the depth cut come out of one walk.  p0 is where the kernel keeps it
+ * anyway (above).  A lane in another medium branches past the walk inside
+ * grid_depth: one piece at rho.  The grid's scalars ride in the kernel argument
+ * (scalar registers); the voxel loads are the only new memory traffic.  The walk's
+ * state lives inside the event only. */
 struct AdvanceIO {
         const double * __restrict__ dir;
         const double * __restrict__ density;  /* [media] */
@@ -2912,15 +2923,20 @@ struct AdvanceIO {
 struct AdvanceLawIO : AdvanceIO {
         const double * __restrict__ scale_height; /* [media] */
 };
+struct AdvanceGridIO : AdvanceIO {
+        turtle_amd_grid_view grid;
+};
 
 /* what a LAW lane keeps of its medium's scale height H: 1 / H, and 0 for the uniform H = HUGE_VAL */
 __device__ __forceinline__ double d_inverse_scale(double H) { return (H == HUGE_VAL) ? 0. : 1. / H; }
 
-template <int MODE, bool FAST, bool LAW = false>
+template <int MODE, bool FAST, bool LAW = false, bool GRID = false>
 __global__ void __launch_bounds__(256) k_advance(tamd_view v, long n, double * __restrict__ pos,
-    int * __restrict__ index, std::conditional_t<LAW, AdvanceLawIO, AdvanceIO> io, ull * __restrict__ stats,
-    ull * __restrict__ queue)
+    int * __restrict__ index,
+    std::conditional_t<GRID, AdvanceGridIO, std::conditional_t<LAW, AdvanceLawIO, AdvanceIO>> io,
+    ull * __restrict__ stats, ull * __restrict__ queue)
 {
+        static_assert(!(LAW && GRID), "a grid together with scale heights is not offered");
         RayQueue q;
         OneCtx ctx;
         d_load_ctx<MODE, FAST>(v, ctx);
@@ -2998,20 +3014,37 @@ __global__ void __launch_bounds__(256) k_advance(tamd_view v, long n, double * _
                                                         x = column_depth(c, w, len);
                                                 }
                                         }
-                                        const bool spent = (X + x >= B), far = (d + len >= M);
+                                        GridDepth walk = { 0., 0., false };
+                                        if constexpr (GRID) {
+                                                /* one walk over what the limit leaves of the step: its depth, or where
+                                                 * the budget runs out inside it (walk.f: there, or the whole of L) */
+                                                double L = (d + len >= M) ? M - d : len;
+                                                if (L > len) L = len;
+                                                walk = grid_depth(io.grid, rho, m, p0x, p0y, p0z, dx, dy, dz, L, B - X);
+                                                x = walk.x;
+                                        }
+                                        const bool spent = GRID ? walk.stopped : (X + x >= B), far = (d + len >= M);
                                         count++;
                                         if (spent | far) { /* the step is cut short, inside medium m */
-                                                double f = far ? M - d : len;
-                                                status = far ? TURTLE_AMD_ADVANCE_DISTANCE : TURTLE_AMD_ADVANCE_SPENT;
-                                                if (spent) {
-                                                        const double fs = LAW ? column_reach(c, w, B - X) : (B - X) / rho;
-                                                        if (fs <= f) f = fs, status = TURTLE_AMD_ADVANCE_SPENT;
+                                                if constexpr (GRID) {
+                                                        const double f = walk.f;
+                                                        status = spent ? TURTLE_AMD_ADVANCE_SPENT : TURTLE_AMD_ADVANCE_DISTANCE;
+                                                        bx = p0x + dx * f, by = p0y + dy * f, bz = p0z + dz * f;
+                                                        X = spent ? B : X + x;
+                                                        d = spent ? d + f : M;
+                                                } else {
+                                                        double f = far ? M - d : len;
+                                                        status = far ? TURTLE_AMD_ADVANCE_DISTANCE : TURTLE_AMD_ADVANCE_SPENT;
+                                                        if (spent) {
+                                                                const double fs = LAW ? column_reach(c, w, B - X) : (B - X) / rho;
+                                                                if (fs <= f) f = fs, status = TURTLE_AMD_ADVANCE_SPENT;
+                                                        }
+                                                        if (f > len) f = len; /* (a rounding guard) */
+                                                        bx = p0x + dx * f, by = p0y + dy * f, bz = p0z + dz * f;
+                                                        const bool by_depth = (status == TURTLE_AMD_ADVANCE_SPENT);
+                                                        X = by_depth ? B : X + (LAW ? column_depth(c, w, f) : rho * f);
+                                                        d = by_depth ? d + f : M;
                                                 }
-                                                if (f > len) f = len; /* (a rounding guard) */
-                                                bx = p0x + dx * f, by = p0y + dy * f, bz = p0z + dz * f;
-                                                const bool by_depth = (status == TURTLE_AMD_ADVANCE_SPENT);
-                                                X = by_depth ? B : X + (LAW ? column_depth(c, w, f) : rho * f);
-                                                d = by_depth ? d + f : M;
                                         } else {
                                                 X += x, d += len;
                                                 if (o.accept) {
@@ -4402,9 +4435,11 @@ extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, cons
 }
 
 /* A whole advance in one launch (k_advance): every tile resident, nothing listed.  scale_height
- * NULL: the instances without the law */
+ * NULL: the instances without the law; grid (host memory, its density a device pointer) not NULL:
+ * the grid instances */
 extern "C" int tamd_k_advance(struct tamd_view view, long n, double * pos, const double * dir,
-    const double * density, const double * scale_height, const double * budget, const double * distance_max,
+    const double * density, const double * scale_height, const struct turtle_amd_grid_view * grid,
+    const double * budget, const double * distance_max,
     double ceiling, int max_steps, int * index, double * depth, double * distance, int * n_steps, int * status,
     unsigned long long * stats, unsigned long long * queue)
 {
@@ -4423,6 +4458,14 @@ extern "C" int tamd_k_advance(struct tamd_view view, long n, double * pos, const
                                 const auto kernel = k_advance<decltype(mode)::value, decltype(fast)::value, true>;
                                 return launch_blocks("k_advance", kernel, persistent_blocks(kernel, n), 0, view, n,
                                     pos, index, law, stats, queue);
+                        }
+                        if (grid != nullptr) {
+                                AdvanceGridIO g;
+                                static_cast<AdvanceIO &>(g) = io;
+                                g.grid = *grid;
+                                const auto kernel = k_advance<decltype(mode)::value, decltype(fast)::value, false, true>;
+                                return launch_blocks("k_advance", kernel, persistent_blocks(kernel, n), 0, view, n,
+                                    pos, index, g, stats, queue);
                         }
                         const auto kernel = k_advance<decltype(mode)::value, decltype(fast)::value>;
                         return launch_blocks("k_advance", kernel, persistent_blocks(kernel, n), 0, view, n, pos,

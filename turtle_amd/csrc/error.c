@@ -126,6 +126,8 @@ const char * turtle_error_function(turtle_function_t * caller)
         NAME(turtle_stepper_crossings_n);
         NAME(turtle_stepper_advance_n);
         NAME(turtle_stepper_advance_exp_n);
+        NAME(turtle_stepper_advance_grid_n);
+        NAME(turtle_amd_grid_enu);
         NAME(turtle_amd_stepper_view_acquire);
         NAME(turtle_amd_stepper_view_release);
         NAME(turtle_stepper_trace_stats);

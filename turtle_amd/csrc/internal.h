@@ -239,11 +239,13 @@ int tamd_k_traverse(struct tamd_view view, long n, double * pos, const double * 
 /* turtle_stepper_advance_n, every tile resident: traverse's loop with a depth budget and an
  * optional distance limit a ray (include/turtle_amd.h states it).  distance_max, depth, distance
  * and n_steps may be NULL.  scale_height [media]: turtle_stepper_advance_exp_n's law (the LAW
- * instances of the kernel), or NULL: every medium uniform (the instances without it).  stats (rays,
- * steps, samples, rays stopped by max_steps) and queue[0] are zeroed by the launcher. */
+ * instances of the kernel), or NULL: every medium uniform (the instances without it).  grid (host
+ * memory, its density a device pointer): turtle_stepper_advance_grid_n's box of voxels (the GRID
+ * instances; not together with scale_height), or NULL.  stats (rays, steps, samples, rays stopped
+ * by max_steps) and queue[0] are zeroed by the launcher. */
 int tamd_k_advance(struct tamd_view view, long n, double * pos, const double * dir,
-    const double * density, const double * scale_height, const double * budget,
-    const double * distance_max, double ceiling, int max_steps, int * index, double * depth,
+    const double * density, const double * scale_height, const struct turtle_amd_grid_view * grid,
+    const double * budget, const double * distance_max, double ceiling, int max_steps, int * index, double * depth,
     double * distance, int * n_steps, int * status, unsigned long long * stats,
     unsigned long long * queue);
 /* the generation-by-generation form over paged stacks: one step of every ray whose index[r][0]

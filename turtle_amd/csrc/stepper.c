@@ -1450,14 +1450,16 @@ enum turtle_return turtle_stepper_crossings_n(struct turtle_stepper * stepper, l
             length, n_steps, n_crossings, &rec, space);
 }
 
-/* turtle_stepper_advance_n and turtle_stepper_advance_exp_n (scale_height, or NULL): resident tiles
+/* turtle_stepper_advance_n, turtle_stepper_advance_exp_n (scale_height, or NULL) and
+ * turtle_stepper_advance_grid_n (grid, or NULL; its voxels staged like any array): resident tiles
  * only (a cut needs the position its step began at, which the generation kernels overwrite): one
  * launch through stepper_resident, and sight_run's closing sequence over a stage of its own. */
 struct advance_args {
         struct tamd_stage stage;
         int paged; /* out: a tile was not resident when the tables were made current */
         long n;
-        void *pos, *dir, *density, *scale_height, *budget, *distance_max, *index, *depth, *distance, *n_steps, *status;
+        void *pos, *dir, *density, *scale_height, *voxels, *budget, *distance_max, *index, *depth, *distance, *n_steps, *status;
+        const struct turtle_amd_grid * grid; /* or NULL */
         double ceiling;
         int max_steps;
 };
@@ -1467,36 +1469,69 @@ static int advance_resident(struct turtle_stepper * stepper, struct tamd_paging 
         struct advance_args * a = p;
         (void)pg, (void)round;
         if ((a->paged = stepper_is_paged(stepper))) return 0; /* (a tile another thread took meanwhile) */
-        return tamd_k_advance(stepper->view, a->n, a->pos, a->dir, a->density, a->scale_height, a->budget,
+        struct turtle_amd_grid_view view, *grid = NULL;
+        if (a->grid != NULL) { /* the caller's box, its voxels where the stage put them */
+                memcpy(view.origin, a->grid->origin, sizeof(view.origin));
+                memcpy(view.axis, a->grid->axis, sizeof(view.axis));
+                memcpy(view.size, a->grid->size, sizeof(view.size));
+                memcpy(view.n, a->grid->n, sizeof(view.n));
+                view.medium = a->grid->medium;
+                view.density = a->voxels;
+                grid = &view;
+        }
+        return tamd_k_advance(stepper->view, a->n, a->pos, a->dir, a->density, a->scale_height, grid, a->budget,
             a->distance_max, a->ceiling, a->max_steps, a->index, a->depth, a->distance, a->n_steps, a->status, stepper->d_stats,
             stepper->d_stats + TAMD_STATS_QUEUE);
 }
 
 static enum turtle_return advance_n(const struct tamd_error * error, struct turtle_stepper * stepper, long n,
     double * position, const double * direction, const double * density, const double * scale_height,
-    const double * budget, const double * distance_max, double altitude_max, int max_steps, int * index,
-    double * depth, double * distance, int * n_steps, int * status, int space)
+    const struct turtle_amd_grid * grid, const double * budget, const double * distance_max,
+    double altitude_max, int max_steps, int * index, double * depth, double * distance, int * n_steps,
+    int * status, int space)
 {
         struct tamd_error error_ = *error;
         if ((stepper == NULL) || (position == NULL) || (direction == NULL) || (density == NULL) ||
             (budget == NULL) || (index == NULL) || (status == NULL))
                 return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
+        if ((grid != NULL) && (grid->density == NULL))
+                return TAMD_RAISE(TURTLE_RETURN_BAD_ADDRESS, "invalid null argument");
         if (max_steps < 0) return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid input parameter(s)");
         if ((space != TURTLE_AMD_HOST) && (space != TURTLE_AMD_DEVICE))
                 return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid space (%d)", space);
+        size_t voxels = 0;
+        if (grid != NULL) {
+                double count = 1.;
+                int i;
+                for (i = 0; i < 3; i++) {
+                        if (grid->n[i] < 1)
+                                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid grid: n[%d] = %d", i, grid->n[i]);
+                        if (!(isfinite(grid->size[i]) && (grid->size[i] > 0.)))
+                                return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid grid: size[%d] = %g", i, grid->size[i]);
+                        count *= grid->n[i];
+                }
+                if (count > INT_MAX)
+                        return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid grid: %d x %d x %d voxels are beyond an int",
+                            grid->n[0], grid->n[1], grid->n[2]);
+                if ((grid->medium < 0) || (grid->medium > stepper->n_layers))
+                        return TAMD_RAISE(TURTLE_RETURN_DOMAIN_ERROR, "invalid grid: medium %d of %d", grid->medium,
+                            stepper->n_layers + 1);
+                voxels = (size_t)count;
+        }
         if (n <= 0) return TURTLE_RETURN_SUCCESS;
         const enum turtle_return loaded =
             stepper_load_all(stepper, &error_, turtle_error_function(error_.function), "advances over");
         if (loaded != TURTLE_RETURN_SUCCESS) return loaded;
         struct advance_args a = { 0 };
         struct tamd_stage * st = &a.stage;
-        a.n = n, a.ceiling = altitude_max, a.max_steps = max_steps;
+        a.n = n, a.ceiling = altitude_max, a.max_steps = max_steps, a.grid = grid;
         const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int);
         const size_t media = (size_t)stepper->n_layers + 1;
         tamd_stage_add(st, position, 3 * nb, TAMD_INOUT, &a.pos);
         tamd_stage_add(st, direction, 3 * nb, TAMD_IN, &a.dir);
         tamd_stage_add(st, density, media * sizeof(double), TAMD_IN, &a.density);
         tamd_stage_add(st, scale_height, media * sizeof(double), TAMD_IN, &a.scale_height);
+        tamd_stage_add(st, (grid != NULL) ? grid->density : NULL, voxels * sizeof(double), TAMD_IN, &a.voxels);
         tamd_stage_add(st, budget, nb, TAMD_IN, &a.budget);
         tamd_stage_add(st, distance_max, nb, TAMD_IN, &a.distance_max);
         tamd_stage_add(st, index, 2 * ni, TAMD_OUT, &a.index);
@@ -1520,7 +1555,7 @@ enum turtle_return turtle_stepper_advance_n(struct turtle_stepper * stepper, lon
     int * status, int space)
 {
         TAMD_ERROR_INIT(&turtle_stepper_advance_n);
-        return advance_n(&error_, stepper, n, position, direction, density, NULL, budget, distance_max,
+        return advance_n(&error_, stepper, n, position, direction, density, NULL, NULL, budget, distance_max,
             altitude_max, max_steps, index, depth, distance, n_steps, status, space);
 }
 
@@ -1530,8 +1565,31 @@ enum turtle_return turtle_stepper_advance_exp_n(struct turtle_stepper * stepper,
     double * distance, int * n_steps, int * status, int space)
 {
         TAMD_ERROR_INIT(&turtle_stepper_advance_exp_n);
-        return advance_n(&error_, stepper, n, position, direction, density, scale_height, budget, distance_max,
+        return advance_n(&error_, stepper, n, position, direction, density, scale_height, NULL, budget,
+            distance_max, altitude_max, max_steps, index, depth, distance, n_steps, status, space);
+}
+
+enum turtle_return turtle_stepper_advance_grid_n(struct turtle_stepper * stepper, long n, double * position,
+    const double * direction, const double * density, const struct turtle_amd_grid * grid,
+    const double * budget, const double * distance_max, double altitude_max, int max_steps, int * index,
+    double * depth, double * distance, int * n_steps, int * status, int space)
+{
+        TAMD_ERROR_INIT(&turtle_stepper_advance_grid_n);
+        return advance_n(&error_, stepper, n, position, direction, density, NULL, grid, budget, distance_max,
             altitude_max, max_steps, index, depth, distance, n_steps, status, space);
+}
+
+/* the east, north, up frame of turtle_ecef_from_horizontal at (latitude, longitude): host arithmetic */
+void turtle_amd_grid_enu(struct turtle_amd_grid * grid, double latitude, double longitude, double height,
+    double east0, double north0, double up0)
+{
+        int i;
+        tamd_h_from_horizontal(latitude, longitude, 90., 0., grid->axis[0]);
+        tamd_h_from_horizontal(latitude, longitude, 0., 0., grid->axis[1]);
+        tamd_h_from_horizontal(latitude, longitude, 0., 90., grid->axis[2]);
+        tamd_h_from_geodetic(latitude, longitude, height, grid->origin);
+        for (i = 0; i < 3; i++)
+                grid->origin[i] += east0 * grid->axis[0][i] + north0 * grid->axis[1][i] + up0 * grid->axis[2][i];
 }
 
 int turtle_amd_stepper_rounds(const struct turtle_stepper * stepper) { return stepper->last_rounds; }
