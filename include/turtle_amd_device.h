@@ -3,7 +3,7 @@
  * your own kernel.  HIP C++ for gfx950 (CDNA4, wave64); include it from a .hip file compiled
  * with hipcc --offload-arch=gfx950 -ffp-contract=off (the STRICT arithmetic reproduces the
  * reference's roundings: a fused multiply-add across them changes bits).  It needs nothing but
- * this directory on the include path.  The library's own kernels (turtle_amd/csrc/device.hip)
+ * this directory on the include path.  The library's own kernels (the .hip files of turtle_amd/csrc)
  * include this same file: there is one source of the arithmetic.
  *
  * The shape of a caller (examples/own_kernel.hip is a complete one):
@@ -117,7 +117,7 @@ enum tamd_kind { TAMD_FLAT = 0, TAMD_MAP = 1, TAMD_STACK = 2 };
 
 /* values of the tile table (tamd_view.tiles) besides a grid index */
 #define TAMD_TILE_NONE (-1)  /* no file for this slot */
-#define TAMD_TILE_PAGED (-2) /* a file, not resident: see "Paging" in device.hip */
+#define TAMD_TILE_PAGED (-2) /* a file, not resident: see "Paging" in csrc/device_common.h */
 
 /* One (data, offset) entry of a layer [ref src/turtle/stepper.h:80-85], stored
  * in the reference's iteration order: last added first [ref stepper.c:722-724] */

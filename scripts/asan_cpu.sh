@@ -11,7 +11,7 @@ cd $ROOT/turtle_amd/csrc
 for f in *.c; do
   gcc -O1 -g -std=gnu99 -fPIC -fsanitize=address,undefined -fno-omit-frame-pointer -I../../include -I. -c $f -o /tmp/asan/${f%.c}.o
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o /tmp/asan/libturtle_amd.so /tmp/asan/*.o build/device.o build/runtime.o -lm -lz -lpthread -fsanitize=address,undefined
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o /tmp/asan/libturtle_amd.so /tmp/asan/*.o $(for f in *.hip; do echo build/${f%.hip}.o; done) -lm -lz -lpthread -fsanitize=address,undefined
 cd $ROOT
 # stage.c alone, against a host-memory stub of the device calls it uses (tests/c/stage_stub.c)
 python -m pytest tests/test_stage_host.py -x -q

@@ -1,11 +1,15 @@
 #!/bin/bash
-# Register / scratch / occupancy of every kernel of device.hip (runs anywhere hipcc does).
-# SRC=tests/c/device_loops.hip or SRC=examples/own_kernel.hip: the kernels written on the device API
-# (include/turtle_amd_device.h), e.g.  SRC=tests/c/device_loops.hip scripts/kernel_resources.sh traverse_trip
+# Register / scratch / occupancy of every kernel of the device layer: the units of the Makefile's
+# DEV_SRC, one after the other (runs anywhere hipcc does).
+# SRC=turtle_amd/csrc/rays.hip: that unit alone; SRC=tests/c/device_loops.hip or
+# SRC=examples/own_kernel.hip: the kernels written on the device API (include/turtle_amd_device.h),
+# e.g.  SRC=tests/c/device_loops.hip scripts/kernel_resources.sh traverse_trip
 cd "$(dirname "$0")/.."
-SRC=${SRC:-turtle_amd/csrc/device.hip}
+SRC=${SRC:-$(sed -n 's/^DEV_SRC *:= *//p' turtle_amd/csrc/Makefile | tr ' ' '\n' | sed 's|^|turtle_amd/csrc/|')}
+for src in $SRC; do
 hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -std=c++17 -Iinclude -Iturtle_amd/csrc \
-  -c "$SRC" -o /tmp/device_res.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
+  -c "$src" -o /tmp/device_res.o -Rpass-analysis=kernel-resource-usage 2>&1
+done | python3 -c "
 import re, sys
 name = None; row = {}
 for line in sys.stdin:

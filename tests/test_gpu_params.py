@@ -540,7 +540,7 @@ def test_edges(math, edge):
     a bisection from a bracket of 25 km leaves).  No ray is set apart.  max_steps bounds every kernel.
 
     A resolution below the 1e-8 m of the bisection's bracket is served by the STRICT kernels in
-    either mode (device.hip, strict_math): with FAST's samples, a few 1e-9 m off, 8 of the 65 rays
+    either mode (device_launch.h, strict_math): with FAST's samples, a few 1e-9 m off, 8 of the 65 rays
     crept over the ground 4 to 32 steps of 1e-9 m earlier or later than the reference's, and 3 of
     them ended on the other side of the 600 steps (rays 0, 34, 37; lengths within 5e-11)."""
     slope, resolution = PC.EDGES[edge]

@@ -1,4 +1,4 @@
-"""The edges of the ray queue that k_walk (queue_refill, device.hip) and k_traverse (its own copy of
+"""The edges of the ray queue that k_walk (queue_refill, device_common.h) and k_traverse (its own copy of
 that loop) draw from, and of the step machine k_walk shares with Stepping::trip() (step_or_bisect,
 turtle_amd_device.h; k_traverse has its own copy of that too).
 

@@ -22,7 +22,7 @@ measures its 20 winners a case), FAST / STRICT:
               layers_geoid 1.83e-12 / 1.83e-12: WORST_TARGET.
 |horizon - fixture| is at most 1.43e-11 / 1.09e-11 (lambert).  No flag differs in any case.
 
-The longitude of a sample is the closed form's atan2 in FAST as well (device.hip, d_sight_sample's
+The longitude of a sample is the closed form's atan2 in FAST as well (sight.hip, d_sight_sample's
 CLOSED_LON).  Observer 0 of layers_geoid stands at longitude 11 exactly and azimuth 0 runs
 due north, along the seam between the stack's tile 10..11 degrees east and the MISSING tile north
 of latitude 1: the reference's transform returns 11 - 1 ulp there, the tile with data, and at 11.0

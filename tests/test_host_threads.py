@@ -27,8 +27,8 @@ def _build(tmp, sanitizer):
             subprocess.check_call(["gcc"] + flags + ["-c", os.path.join(CSRC, f), "-o", objs[-1]])
     lib = os.path.join(out, "libturtle_amd.so")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-o", lib] + objs +
-                          [os.path.join(CSRC, "build", "device.o"), os.path.join(CSRC, "build", "runtime.o"),
-                           "-lm", "-lz", "-lpthread",
+                          [os.path.join(CSRC, "build", f[:-4] + ".o") for f in sorted(os.listdir(CSRC))
+                           if f.endswith(".hip")] + ["-lm", "-lz", "-lpthread",
                            f"-fsanitize={sanitizer}"])
     exe = os.path.join(out, "host_stack_threads")
     subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", f"-fsanitize={sanitizer}",

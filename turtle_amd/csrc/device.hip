@@ -1,11 +1,13 @@
 /*
- * device.hip -- the gfx950 device layer of libturtle_amd: every kernel of the
- * stepper path, and the layer that launches them.  (The calling thread's device,
- * stream and memory: runtime.hip.)  Written for CDNA4 (wave64); no other target
- * is supported.
+ * device.hip -- the hot unit of the gfx950 device layer of libturtle_amd: the kernels
+ * of a trace, of a batch of single steps and of a scattering walk, the small ones
+ * around them, and the layer that launches them.  The other families have a unit
+ * each (points.hip, maps.hip, sight.hip, rays.hip); what the units share is in
+ * device_common.h and device_launch.h.  (The calling thread's device, stream and
+ * memory: runtime.hip.)  Written for CDNA4 (wave64); no other target is supported.
  *
  * Arithmetic contract: the kernels evaluate the reference's expressions in
- * the reference's operand order in IEEE fp64 (this file is compiled with
+ * the reference's operand order in IEEE fp64 (every unit is compiled with
  * -ffp-contract=off, so no FMA is formed across the reference's roundings).
  * +, -, *, / and sqrt are correctly rounded on gfx950, so they agree bit for
  * bit with the x86 reference; sin/cos/asin/acos/atan2 come from ROCm's OCML
@@ -17,43 +19,25 @@
  * a cubic Taylor line along each long ray: see the comments at f_to_geodetic,
  * RayLine, PhaseIO and k_trace, and DESIGN.md 3.1.
  *
- * Kernels (one thread = one ray/point; all are fp64 VALU work with a 4-node
+ * Kernels (one thread = one ray; all are fp64 VALU work with a 4-node
  * 16-bit gather per sample, see DESIGN.md for the roofline of each):
- *   k_ecef_*        batch ECEF transforms              [ref ecef.c:41-207]
- *   k_elevation     batch bilinear lookup, map/stack   [ref map.c:229-277, stack.c:300-361]
- *   k_position      batch turtle_stepper_position      [ref stepper.c:877-931]
- *   k_normal        batch normals of a layer's top surface (turtle_stepper_normal_n)
- *   k_horizon       the skyline around observers, one wave per line of sight: the highest of a
- *                   line's samples of a layer's top (turtle_stepper_horizon_n)
- *   k_viewshed      which samples of those lines the observer sees: a wave-wide prefix maximum
- *                   over chunks of 64 samples (turtle_stepper_viewshed_n)
- *   k_clearance     the least height of the chord from an observer to a target above a layer's
- *                   top, one wave per line (turtle_stepper_clearance_n)
  *   k_step          batch turtle_stepper_step [ref stepper.c:780-875]: the sample and
  *   k_step_fast     the tentative step; rays that crossed a boundary are listed
  *                   (k_step_fast: the fast-math body of the one-map / one-stack
  *                   modes held to 128 registers)
  *   k_bisect        ... and bisected here, packed [ref stepper.c:836-864]
- *   k_gradient, k_project   batch gradients and map projections
  *   k_trace         persistent-wave trace-to-boundary loop (the hot kernel: trace_body)
  *   k_first         a fast trace's first closed-form steps, flat: a ray a lane
  *   k_cross         the crossings a trace's passes listed, located by halving
  *   k_ray_cells     the cell each ray starts over: the key a large trace orders its rays by
  *   k_walk          a whole scattering walk per ray, in registers (turtle_stepper_scatter_n)
- *   k_traverse      a line of sight per ray through every medium, every tile resident
- *                   (turtle_stepper_traverse_n; <REC>: turtle_stepper_crossings_n)
- *   k_traverse_gen, k_crossings_gen   the same over paged stacks: the accounting after each
- *                   generation of k_step + k_bisect
- *   k_resample      a whole map from a stack or a map (turtle_map_resample)
- *   k_fill_encode, k_fill_store, k_nodes   windows of nodes (turtle_map_fill_n, _node_n)
- *   k_unblock       the host copy of a map from its HBM copy
  *   k_isotropic, k_philox   Philox-4x32-10: isotropic directions, raw words (scattering harness)
  *   k_order_count, k_order_place   a trace's hand-over list in the order of its one-byte keys: a
  *                   counting sort between the two passes
  *   k_tally         hit counts + path-length histogram (uint64, exact): a block a CU at the most
  */
 #include <hip/hip_runtime.h>
-#include <hipcub/device/device_radix_sort.hpp>
+#include <hipcub/device/device_radix_sort.hpp> /* (RoomSort's alone: no other unit pays for it) */
 
 #include <cfloat>
 #include <cstdio>
@@ -61,680 +45,15 @@
 #include <cstring>
 #include <type_traits>
 
-#include "device_ctx.h"
-#include "internal.h" /* includes turtle_amd_device.h: the device functions and the tables */
+#include "device_common.h"
+#include "device_launch.h"
 #include "trace_room.h"
 
-using namespace turtle_amd_device;
-
 namespace {
-
-/* ---- wave idioms ---------------------------------------------------------
- *
- * What the kernels below do a wave at a time. */
-
-/* this lane's rank among the lanes of `mask` (a ballot): how many of them are below it */
-__device__ __forceinline__ int lane_rank(ull mask)
-{
-        return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-}
-
-/* The ray queue of k_walk: a counter in HBM from which a wave draws `chunk` ray numbers at a time
- * with one atomic (wave-aggregated), so the queue sees n / chunk atomics.  (trace_body keeps a
- * refill of its own: the paged wait, the pool and the ordered input are woven in.  So does
- * k_traverse, and its own copy of the step machine: see there.) */
-struct RayQueue {
-        long next = 0, end = 0; /* wave-uniform: the numbers drawn and not yet given to a lane */
-        bool exhausted = false; /* wave-uniform: the queue has run dry */
-};
-
-/* Refill the idle lanes (ray < 0 and not `dead`), whole wave: a lane gets its number in `ray` and
- * take() loads that ray -- or sets `ray` below 0 again for one with nothing to do, and the lane
- * draws again.  A lane that still needs a ray when the queue is dry is `dead`. */
-template <class Take>
-__device__ __forceinline__ void queue_refill(RayQueue & q, ull * __restrict__ queue, int chunk, long n,
-    long & ray, bool & dead, Take && take)
-{
-        for (;;) {
-                const bool need = (ray < 0) && !dead;
-                const ull mask = __ballot(need);
-                if (mask == 0) break;
-                if (q.next >= q.end) {
-                        if (q.exhausted) {
-                                if (need) dead = true;
-                                break;
-                        }
-                        ull base = 0;
-                        if ((threadIdx.x & 63) == 0) base = atomicAdd(queue, (ull)chunk);
-                        base = __shfl(base, 0, 64);
-                        q.next = (long)base;
-                        q.end = min((long)base + chunk, n);
-                        if ((long)base >= n) {
-                                q.exhausted = true;
-                                q.next = q.end = 0;
-                        }
-                        continue;
-                }
-                const long avail = q.end - q.next;
-                const int rank = lane_rank(mask);
-                if (need && (rank < avail)) {
-                        ray = q.next + rank;
-                        take();
-                }
-                q.next += min((long)__popcll(mask), avail);
-        }
-}
 
 /* ======================================================================== */
 /*                                 kernels                                  */
 /* ======================================================================== */
-
-__global__ void k_ecef_from_geodetic(long n, const double * __restrict__ lat,
-    const double * __restrict__ lon, const double * __restrict__ elev,
-    double * __restrict__ ecef)
-{
-        for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
-             r += (long)gridDim.x * blockDim.x) {
-                double x, y, z;
-                d_from_geodetic(lat[r], lon[r], elev[r], x, y, z);
-                ecef[3 * r] = x, ecef[3 * r + 1] = y, ecef[3 * r + 2] = z;
-        }
-}
-
-template <bool FAST>
-__global__ void k_ecef_to_geodetic(long n, const double * __restrict__ ecef,
-    double * __restrict__ lat, double * __restrict__ lon, double * __restrict__ alt)
-{
-        for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
-             r += (long)gridDim.x * blockDim.x) {
-                double la, lo, al;
-                if (FAST)
-                        f_to_geodetic(ecef[3 * r], ecef[3 * r + 1], ecef[3 * r + 2], la, lo, al);
-                else
-                        d_to_geodetic(ecef[3 * r], ecef[3 * r + 1], ecef[3 * r + 2], la, lo, al);
-                if (lat) lat[r] = la;
-                if (lon) lon[r] = lo;
-                if (alt) alt[r] = al;
-        }
-}
-
-/* [ref ecef.c:160-176] */
-__global__ void k_ecef_from_horizontal(long n, const double * __restrict__ lat,
-    const double * __restrict__ lon, const double * __restrict__ az_,
-    const double * __restrict__ el_, double * __restrict__ dir)
-{
-        for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
-             r += (long)gridDim.x * blockDim.x) {
-                double e[3], nn[3], u[3];
-                d_enu(lat[r], lon[r], e, nn, u);
-                const double az = az_[r] * kPi / 180.;
-                const double el = el_[r] * kPi / 180.;
-                const double ce = cos(el);
-                const double q0 = ce * sin(az), q1 = ce * cos(az), q2 = sin(el);
-                for (int i = 0; i < 3; i++)
-                        dir[3 * r + i] = q0 * e[i] + q1 * nn[i] + q2 * u[i];
-        }
-}
-
-/* [ref ecef.c:178-207] */
-__global__ void k_ecef_to_horizontal(long n, const double * __restrict__ lat,
-    const double * __restrict__ lon, const double * __restrict__ dir,
-    double * __restrict__ az, double * __restrict__ el)
-{
-        for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
-             r += (long)gridDim.x * blockDim.x) {
-                double e[3], nn[3], u[3];
-                d_enu(lat[r], lon[r], e, nn, u);
-                const double d0 = dir[3 * r], d1 = dir[3 * r + 1], d2 = dir[3 * r + 2];
-                const double x = e[0] * d0 + e[1] * d1 + e[2] * d2;
-                const double y = nn[0] * d0 + nn[1] * d1 + nn[2] * d2;
-                const double z = u[0] * d0 + u[1] * d1 + u[2] * d2;
-                double rr = d0 * d0 + d1 * d1 + d2 * d2;
-                if (rr <= FLT_EPSILON) continue; /* outputs untouched [ref ecef.c:194] */
-                rr = sqrt(rr);
-                if (az) az[r] = atan2(x, y) * 180. / kPi;
-                if (el) {
-                        const double arg = z / rr;
-                        el[r] = (arg > 1.) ? 90. :
-                                             ((arg < -1.) ? -90. : asin(arg) * 180. / kPi);
-                }
-        }
-}
-
-__global__ void k_project(tamd_proj pr, int inverse, long n, const double * __restrict__ a,
-    const double * __restrict__ b, double * __restrict__ c, double * __restrict__ d)
-{
-        for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
-             r += (long)gridDim.x * blockDim.x) {
-                double u, w;
-                if (inverse)
-                        d_unproject(pr, a[r], b[r], u, w);
-                else
-                        d_project(pr, a[r], b[r], u, w);
-                c[r] = u, d[r] = w;
-        }
-}
-
-/* One round of a batch call over a geometry with paged tiles (see tile_fault).
- * ids / n_in: the rays or points of this round (NULL: all of 0 .. n-1, the first
- * round); faulted / n_faulted / wanted: where to list those that need a tile
- * that is not resident, and a bitmap, over the tile table, of the tiles they
- * need.  All NULL for a geometry with every tile resident. */
-typedef struct tamd_paging Paging;
-
-/* the whole wave calls: lists the lanes with a fault (one atomic per wave), and
- * counts, tile by tile, how many listed items want it (the host keeps the tiles
- * in demand) -- the tiles of the very first item of the list go into the
- * bitmap `wanted_first` too: the host serves that one without fail, so that
- * every round completes at least one item whatever the others compete for */
-__device__ __forceinline__ void page_fault(const Paging & pg, const TileFault & f, long r,
-    int also = -1 /* one more tile the item wants kept: where it resumes from */)
-{
-        const bool fault = f.centre >= 0;
-        const ull mask = __ballot(fault);
-        if (mask == 0) return;
-        const int leader = __builtin_ctzll(mask);
-        ull base = 0;
-        if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(pg.n_faulted, (ull)__popcll(mask));
-        base = __shfl(base, leader, 64);
-        if (fault) {
-                const int rank = lane_rank(mask);
-                pg.faulted[base + rank] = (int)r;
-                /* the item the host serves without fail: the one it named, else the
-                 * first of this list (which it will name from the next round on) */
-                const bool first = (pg.first_id >= 0) ? (r == (long)pg.first_id) : ((base + rank) == 0);
-                for (int b = 0; b < 9; b++) {
-                        if (!((f.mask >> b) & 1)) continue;
-                        const int t = f.centre + (b / 3 - 1) * f.stride + (b % 3 - 1);
-                        if (b != 4) atomicAdd(&pg.wanted[(size_t)t * TAMD_DEMAND_STRIDE], 1u); /* (the centre: below) */
-                        if (first) atomicOr(&pg.wanted_first[t >> 5], 1u << (t & 31));
-                }
-                if (also >= 0) {
-                        atomicAdd(&pg.wanted[(size_t)also * TAMD_DEMAND_STRIDE], 1u);
-                        if (first) atomicOr(&pg.wanted_first[also >> 5], 1u << (also & 31));
-                }
-        }
-        /* the tile an item is IN: one addition per wave and tile (the rays of a batch that start
-         * over tiles not resident fault together, a wave at a time, on a handful of tiles) */
-        const bool centre = fault && (((f.mask >> 4) & 1) != 0);
-        ull left = __ballot(centre);
-        while (left != 0) {
-                const int lead = __builtin_ctzll(left);
-                const int t0 = __shfl(f.centre, lead, 64);
-                const ull same = __ballot(centre && (f.centre == t0));
-                if ((int)(threadIdx.x & 63) == lead)
-                        atomicAdd(&pg.wanted[(size_t)t0 * TAMD_DEMAND_STRIDE], (unsigned)__popcll(same));
-                left &= ~same;
-        }
-}
-
-/* Loop of the one-thread-per-item kernels: whole waves go round (page_fault is
- * a wave-wide call); `r` is the item of this lane, or -1 */
-#define PAGED_ITEMS(pg, n, i0, r)                                                              \
-        const long n_items_ = ((pg).n_in != nullptr) ? (long)*(pg).n_in : (n);                 \
-        for (long i0 = blockIdx.x * (long)blockDim.x; i0 < n_items_;                           \
-             i0 += (long)gridDim.x * blockDim.x)                                               \
-                for (long i_ = i0 + threadIdx.x, r = (i_ < n_items_) ?                         \
-                             (((pg).ids != nullptr) ? (long)(pg).ids[i_] : i_) : -1, once_ = 1; \
-                     once_; once_ = 0)
-
-/* Elevation of n points on the view's first meta.  For a MAP the arguments
- * are (x, y) [ref map.c:380-385]; for a STACK (latitude, longitude)
- * [ref stack.c:338-361]. */
-__global__ void k_elevation(tamd_view v, long n, const double * __restrict__ a,
-    const double * __restrict__ b, double * __restrict__ z, int * __restrict__ inside, Paging pg)
-{
-        const tamd_meta mt = v.metas[0];
-        PAGED_ITEMS(pg, n, i0, r)
-        {
-                int in = 0;
-                TileFault f = { -1, 0, 0 };
-                if (r >= 0) {
-                        double zz = 0.;
-                        if (mt.kind == TAMD_MAP)
-                                in = d_grid_elevation(v.grids[mt.src], a[r], b[r], zz) ? 1 : 0;
-                        else
-                                in = d_stack_elevation(v, v.stacks[mt.src], a[r], b[r], zz, f);
-                        if (in >= 0) f.centre = -1;
-                        if (in >= 0) {
-                                /* an outside point leaves a MAP's z untouched in the
-                                 * reference and zeroes a STACK's; report 0 for both */
-                                z[r] = in ? zz : 0.;
-                                inside[r] = in;
-                        }
-                }
-                if (pg.faulted != nullptr) page_fault(pg, f, r);
-        }
-}
-
-/* Gradient of n points on the view's first meta: a MAP takes (x, y) and
- * returns (gx, gy) [ref map.c:387-392]; a STACK takes (latitude, longitude)
- * and returns (glat, glon) [ref stack.c:364-388].  Outputs are in-out. */
-__global__ void k_gradient(tamd_view v, long n, const double * __restrict__ a,
-    const double * __restrict__ b, double * __restrict__ ga, double * __restrict__ gb,
-    int * __restrict__ inside, Paging pg)
-{
-        const tamd_meta mt = v.metas[0];
-        PAGED_ITEMS(pg, n, i0, r)
-        {
-                int tile = 0;
-                TileFault f = { -1, 0, 0 };
-                if (r >= 0) {
-                        bool in = false;
-                        if (mt.kind == TAMD_MAP) {
-                                double gx = ga[r], gy = gb[r];
-                                in = d_grid_gradient(v.grids[mt.src], a[r], b[r], gx, gy);
-                                ga[r] = gx, gb[r] = gy;
-                        } else {
-                                tile = d_stack_tile(v, v.stacks[mt.src], a[r], b[r], f);
-                                if (tile != kTileFault) f.centre = -1;
-                                if (tile == -1) {
-                                        ga[r] = gb[r] = 0.; /* [ref stack.c:378-382] */
-                                } else if (tile >= 0) {
-                                        double glat = ga[r], glon = gb[r];
-                                        /* x = longitude, y = latitude; gx -> glon, gy -> glat */
-                                        in = d_grid_gradient(v.grids[tile], b[r], a[r], glon, glat);
-                                        ga[r] = glat, gb[r] = glon;
-                                }
-                        }
-                        if (tile != kTileFault) inside[r] = in ? 1 : 0;
-                }
-                if (pg.faulted != nullptr) page_fault(pg, f, r);
-        }
-}
-
-/* [ref stepper.c:877-931] */
-__global__ void k_position(tamd_view v, long n, const double * __restrict__ lat,
-    const double * __restrict__ lon, const double * __restrict__ height, int layer,
-    double * __restrict__ pos, int * __restrict__ data_index, Paging pg)
-{
-        PAGED_ITEMS(pg, n, i0, r)
-        {
-                TileFault fault = { -1, 0, 0 };
-                if (r >= 0) {
-                        const double la = lat[r], lo = lon[r];
-                        int found = -1, di = 0;
-                        double elevation = 0.;
-                        const int end = v.layer_first[layer + 1];
-                        for (int j = v.layer_first[layer]; j < end; j++, di++) {
-                                const tamd_meta mt = v.metas[j];
-                                TileFault f;
-                                const int in = d_source_elevation(v, mt, la, lo, elevation, f);
-                                if (in < 0) {
-                                        fault = f;
-                                        break;
-                                }
-                                if (in == 0) continue;
-                                elevation += mt.offset;
-                                if (v.geoid >= 0) { /* [ref stepper.c:905-914] */
-                                        double undulation;
-                                        const double l360 = (lo >= 0) ? lo : lo + 360.;
-                                        if (d_grid_elevation(
-                                                v.grids[v.geoid], l360, la, undulation))
-                                                elevation += undulation;
-                                }
-                                found = di;
-                                break;
-                        }
-                        if (fault.centre < 0) {
-                                data_index[r] = found;
-                                if (found >= 0) {
-                                        double x, y, z;
-                                        d_from_geodetic(la, lo, elevation + height[r], x, y, z);
-                                        pos[3 * r] = x, pos[3 * r + 1] = y, pos[3 * r + 2] = z;
-                                }
-                        }
-                }
-                if (pg.faulted != nullptr) page_fault(pg, fault, r);
-        }
-}
-
-/* turtle_stepper_normal_n: the normal of the top of layer[r] above or below pos[r], one point per
- * lane; the arithmetic is normal()'s of turtle_amd_device.h, always the strict one.  A point with
- * no data there (or no such layer) gets data_index -1 and keeps its row of `out`. */
-template <int MODE>
-__global__ void __launch_bounds__(256) k_normal(tamd_view v, long n, const double * __restrict__ pos,
-    const int * __restrict__ layer, double * __restrict__ out, int * __restrict__ data_index, Paging pg)
-{
-        const Geometry<MODE, STRICT> geo(v);
-        PAGED_ITEMS(pg, n, i0, r)
-        {
-                TileFault fault = { -1, 0, 0 };
-                if (r >= 0) {
-                        const double p[3] = { pos[3 * r], pos[3 * r + 1], pos[3 * r + 2] };
-                        double w[3];
-                        TileFault f = { -1, 0, 0 };
-                        const int found = normal(geo, p, layer[r], w, &f);
-                        if (found == kTileFault) {
-                                fault = f;
-                        } else {
-                                data_index[r] = found;
-                                if (found >= 0) out[3 * r] = w[0], out[3 * r + 1] = w[1], out[3 * r + 2] = w[2];
-                        }
-                }
-                if (pg.faulted != nullptr) page_fault(pg, fault, r);
-        }
-}
-
-/* The top of `layer` under (la, lo) as turtle_stepper_position finds it [ref stepper.c:892-914]:
- * the layer's data last added first, the offset, the geoid -- k_position's arithmetic, always the
- * strict one.  false where no data answers; a tile that is not resident answers nothing (the
- * callers run over resident geometry). */
-template <int MODE>
-__device__ __forceinline__ bool d_layer_top(const tamd_view & v, const OneCtx & ctx, int layer, double la,
-    double lo, double & elevation)
-{
-        TileFault f;
-        if (MODE == TAMD_MODE_ONE_MAP) {
-                if (!d_grid_elevation<false>(ctx.grid, lo, la, elevation)) return false;
-                elevation += ctx.offset;
-                return true;
-        }
-        if (MODE == TAMD_MODE_ONE_STACK) {
-                if (d_stack_elevation<false>(v, ctx.stack, la, lo, elevation, f) <= 0) return false;
-                elevation += ctx.offset;
-                return true;
-        }
-        const int end = v.layer_first[layer + 1];
-        for (int j = v.layer_first[layer]; j < end; j++) {
-                const tamd_meta mt = v.metas[j];
-                const int in = d_source_elevation(v, mt, la, lo, elevation, f);
-                if (in < 0) return false;
-                if (in == 0) continue;
-                elevation += mt.offset;
-                if (v.geoid >= 0) {
-                        double undulation;
-                        const double l360 = (lo >= 0) ? lo : lo + 360.;
-                        if (d_grid_elevation(v.grids[v.geoid], l360, la, undulation)) elevation += undulation;
-                }
-                return true;
-        }
-        return false;
-}
-
-/* A line of sight of turtle_stepper_horizon_n and _viewshed_n: line a of observer r. */
-struct SightLine {
-        double p0, p1, p2; /* the observer */
-        double u[3];       /* its vertical */
-        double h[3];       /* the line's horizontal unit vector: the sample at distance s lies under p + s h */
-};
-
-/* The preamble of both kernels: the observer's geodetic coordinates, its frame, and h from the
- * azimuth.  Wave-uniform, computed by every lane.  FAST: the to_geodetic transform only. */
-template <bool FAST>
-__device__ __forceinline__ void d_sight_line(const double * __restrict__ pos,
-    const double * __restrict__ azimuth, long r, int a, SightLine & line)
-{
-        const double p0 = pos[3 * r], p1 = pos[3 * r + 1], p2 = pos[3 * r + 2];
-        double lat0, lon0, alt0;
-        if (FAST)
-                f_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
-        else
-                d_to_geodetic(p0, p1, p2, lat0, lon0, alt0);
-        double e[3], nn[3];
-        d_enu(lat0, lon0, e, nn, line.u);
-        { /* turtle_ecef_from_horizontal at elevation 0 [ref ecef.c:160-176] */
-                const double az = azimuth[a] * kPi / 180.;
-                const double el = 0. * kPi / 180.;
-                const double ce = cos(el);
-                const double q0 = ce * sin(az), q1 = ce * cos(az), q2 = sin(el);
-                for (int j = 0; j < 3; j++) line.h[j] = q0 * e[j] + q1 * nn[j] + q2 * line.u[j];
-        }
-        line.p0 = p0, line.p1 = p1, line.p2 = p2;
-}
-
-/* One sample of a line: the sine of the elevation angle of the layer's top under p + s h as the
- * observer p sees it (`ground`, at `range`), and of the point `height` above it (`target`; the
- * ground's own at height 0).  false where the definition skips the sample: no data there, or a
- * point at the observer itself [ref ecef.c:194].  FAST: the to_geodetic transform only;
- * everything else is the strict arithmetic.
- *
- * CLOSED_LON is the one deliberate difference between the two calls ("The seam"): in
- * FAST arithmetic, true takes the sample's longitude from the closed form's atan2 [ref ecef.c:86],
- * false keeps the fast transform's; STRICT has the closed form's either way.  k_viewshed passes
- * true: a line due north or south of an observer on a whole degree runs ALONG a seam of the tiles,
- * the last ulp of the longitude then says which tile answers -- beside a missing tile, whether a
- * sample has data at all -- and the call reports every sample, so with the reference's expression
- * its flags are the reference's there too.  k_horizon passes false: such a sample changes a
- * skyline only if it was the winner, and its FAST outputs stay what they were.
- *
- * RANGE: `range` is returned (k_horizon); without it (k_viewshed) the parameter is left alone.  The
- * operations are the same, sqrt then `/` (DESIGN 3.14 has what the switch is worth). */
-template <int MODE, bool FAST, bool CLOSED_LON, bool RANGE>
-__device__ __forceinline__ bool d_sight_sample(const tamd_view & v, const OneCtx & ctx, int layer,
-    const SightLine & line, double s, double height, double & ground, double & target, double & range)
-{
-        const double p0 = line.p0, p1 = line.p1, p2 = line.p2;
-        const double x = p0 + s * line.h[0], y = p1 + s * line.h[1], z = p2 + s * line.h[2];
-        double la, lo, al, top;
-        if (FAST) {
-                f_to_geodetic(x, y, z, la, lo, al);
-                if (CLOSED_LON && ((x != 0.) || (y != 0.))) lo = atan2(y, x) * 180. / kPi;
-        } else
-                d_to_geodetic(x, y, z, la, lo, al);
-        if (!d_layer_top<MODE>(v, ctx, layer, la, lo, top)) return false;
-        double g0, g1, g2;
-        d_from_geodetic(la, lo, top + 0., g0, g1, g2);
-        double d0 = g0 - p0, d1 = g1 - p1, d2 = g2 - p2;
-        double rr = d0 * d0 + d1 * d1 + d2 * d2;
-        if (rr <= FLT_EPSILON) return false;
-        if (RANGE) {
-                range = sqrt(rr);
-                ground = (line.u[0] * d0 + line.u[1] * d1 + line.u[2] * d2) / range;
-        } else
-                ground = (line.u[0] * d0 + line.u[1] * d1 + line.u[2] * d2) / sqrt(rr);
-        if (height == 0.) {
-                target = ground;
-                return true;
-        }
-        d_from_geodetic(la, lo, top + height, g0, g1, g2);
-        d0 = g0 - p0, d1 = g1 - p1, d2 = g2 - p2;
-        rr = d0 * d0 + d1 * d1 + d2 * d2;
-        if (rr <= FLT_EPSILON) return false;
-        target = (line.u[0] * d0 + line.u[1] * d1 + line.u[2] * d2) / sqrt(rr);
-        return true;
-}
-
-/* turtle_stepper_horizon_n: the skyline around observers.  One WAVE per item i = r * n_az + a
- * (line a of observer r), four items a block; lane l takes the samples k = l, l + 64, ... of the
- * line and keeps its own best (sine of the elevation angle, k + 1, range); the wave then reduces
- * the 64 triples with a butterfly of shuffles under the order "larger sine, then smaller k", which
- * is what the strict `>` of the sequential loop gives, and lane 0 writes.  The observer's preamble
- * (its geodetic coordinates, the frame, the horizontal unit vector) is wave-uniform and computed by
- * every lane.  FAST: the two to_geodetic transforms only; everything else is the strict
- * arithmetic.  No paging: the geometry is resident. */
-template <int MODE, bool FAST>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_horizon(tamd_view v, int n_items, int n_az, int n_d,
-    const double * __restrict__ pos, const double * __restrict__ azimuth,
-    const double * __restrict__ distance, int layer, double * __restrict__ elevation,
-    int * __restrict__ sample, double * __restrict__ range)
-{
-        OneCtx ctx;
-        d_load_ctx<MODE, false>(v, ctx);
-        const int lane = (int)(threadIdx.x & 63);
-        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        for (long i = blockIdx.x * 4L + wave; i < (long)n_items; i += (long)gridDim.x * 4L) {
-                const long r = i / n_az;
-                const int a = (int)(i - r * n_az);
-                SightLine line;
-                d_sight_line<FAST>(pos, azimuth, r, a, line);
-
-                double best = -HUGE_VAL, best_range = 0.;
-                int best_k = 0;
-                for (int k = lane; k < n_d; k += 64) {
-                        /* (set: left undefined where the sample is skipped, they cost 12 to 24 B of scratch) */
-                        double arg = 0., same = 0., rr = 0.;
-                        if (!d_sight_sample<MODE, FAST, false, true>(v, ctx, layer, line, distance[k], 0., arg, same, rr))
-                                continue;
-                        if (arg > best) best = arg, best_k = k + 1, best_range = rr; /* (a NaN never wins) */
-                }
-                for (int off = 32; off > 0; off >>= 1) {
-                        const double o_best = __shfl_xor(best, off, 64);
-                        const double o_range = __shfl_xor(best_range, off, 64);
-                        const int o_k = __shfl_xor(best_k, off, 64);
-                        /* (a lane without a sample holds (-inf, 0): it never wins, and loses to any) */
-                        if ((o_best > best) || ((o_best == best) && (o_k != 0) && (o_k < best_k)))
-                                best = o_best, best_k = o_k, best_range = o_range;
-                }
-                if (lane == 0) {
-                        sample[i] = best_k;
-                        if (best_k != 0) {
-                                elevation[i] = (best > 1.) ? 90. : ((best < -1.) ? -90. : asin(best) * 180. / kPi);
-                                if (range != nullptr) range[i] = best_range;
-                        }
-                }
-        }
-}
-
-/* turtle_stepper_viewshed_n: which samples of a line the observer sees.  One WAVE per item
- * i = r * n_az + a as in k_horizon, four items a block, but a line is swept in CHUNKS of 64
- * consecutive samples, k = base + lane: sample k is seen iff the target's sine is not below the
- * maximum of the ground's sines of the samples before it, a prefix maximum.  Per chunk every lane
- * evaluates its sample; an inclusive Hillis-Steele scan over the lanes (__shfl_up by 1 .. 32)
- * gives the maximum up to each lane, the value one lane below (and `carry`, the maximum of the
- * chunks before, wave-uniform) the horizon in front of it.  The chunk loop's bound is wave-uniform
- * and nothing branches around the scan: a lane past the end, a skipped sample and a NaN contribute
- * -HUGE_VAL.  A maximum rounds nothing, and of equal values (+0 and -0) the earlier one is kept
- * as the sequential `>` keeps it: the outputs are the sequential loop's bits.  Lane l writes
- * element base + l of each output; no LDS, no atomics, no scratch. */
-template <int MODE, bool FAST>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_viewshed(tamd_view v, int n_items, int n_az, int n_d,
-    const double * __restrict__ pos, const double * __restrict__ azimuth,
-    const double * __restrict__ distance, int layer, double height, signed char * __restrict__ visible,
-    double * __restrict__ sine, double * __restrict__ horizon, int * __restrict__ n_visible)
-{
-        OneCtx ctx;
-        d_load_ctx<MODE, false>(v, ctx);
-        const int lane = (int)(threadIdx.x & 63);
-        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        for (long i = blockIdx.x * 4L + wave; i < (long)n_items; i += (long)gridDim.x * 4L) {
-                const long r = i / n_az;
-                const int a = (int)(i - r * n_az);
-                SightLine line;
-                d_sight_line<FAST>(pos, azimuth, r, a, line);
-
-                const size_t first = (size_t)i * (size_t)n_d;
-                double carry = -HUGE_VAL;
-                int count = 0;
-                for (int base = 0; base < n_d; base += 64) { /* (wave-uniform: every lane reaches every shuffle) */
-                        const int k = base + lane;
-                        const bool in = k < n_d;
-                        double ground = -HUGE_VAL, target = -HUGE_VAL;
-                        bool data = false;
-                        if (in) {
-                                double rr; /* (RANGE false: not written) */
-                                data = d_sight_sample<MODE, FAST, true, false>(v, ctx, layer, line, distance[k], height,
-                                    ground, target, rr);
-                        }
-                        /* (ground == ground: a NaN never raises the horizon) */
-                        double inclusive = (data && (ground == ground)) ? ground : -HUGE_VAL;
-                        for (int off = 1; off < 64; off <<= 1) {
-                                const double lower = __shfl_up(inclusive, off, 64);
-                                if (lane >= off) inclusive = (inclusive > lower) ? inclusive : lower;
-                        }
-                        double before = __shfl_up(inclusive, 1, 64);
-                        if (lane == 0) before = -HUGE_VAL;
-                        before = (before > carry) ? before : carry;
-                        const double last = __shfl(inclusive, 63, 64);
-                        carry = (last > carry) ? last : carry;
-                        const bool seen = data && (target >= before); /* (a NaN is never seen; grazing is) */
-                        count += __popcll(__ballot(seen));
-                        if (in) {
-                                visible[first + k] = data ? (signed char)seen : (signed char)-1;
-                                if (sine != nullptr) sine[first + k] = data ? target : __builtin_nan("");
-                                if (horizon != nullptr) horizon[first + k] = before;
-                        }
-                }
-                if ((n_visible != nullptr) && (lane == 0)) n_visible[i] = count;
-        }
-}
-
-/* turtle_stepper_clearance_n: the minimum clearance of the straight chord from an observer to a
- * target above a layer's top.  One WAVE per item (i = r * n_t + t, or i = r with PAIRED), four
- * items a block, as in k_horizon; lane l takes the samples k = l, l + 64, ... at the fractions
- * fraction[k] of the chord and keeps its own (least clearance, k + 1, number of samples with
- * data); the wave reduces the 64 pairs with a butterfly of shuffles under the order "smaller
- * clearance, then smaller k", which is what the strict `<` of the sequential loop gives, sums the
- * counts, and lane 0 writes.  The chord's ends and their difference are wave-uniform.  A sample's
- * transform is d_sight_sample's with CLOSED_LON (FAST: latitude from the fast transform, longitude
- * from the closed form's atan2, so that a sample has data where the reference says it has);
- * everything else is the strict arithmetic.  The ground under the sample (d_from_geodetic) and the
- * sample's vertical (d_enu's u) are written with the same expressions of the same latitude and
- * longitude: one set of sines and cosines serves both.  No paging: the geometry is resident. */
-template <int MODE, bool FAST>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_clearance(tamd_view v, int n_items, int n_t, int paired,
-    int n_f, const double * __restrict__ observer, const double * __restrict__ target,
-    const double * __restrict__ fraction, int layer, double * __restrict__ clearance,
-    int * __restrict__ sample, int * __restrict__ n_data)
-{
-        OneCtx ctx;
-        d_load_ctx<MODE, false>(v, ctx);
-        const int lane = (int)(threadIdx.x & 63);
-        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        for (long i = blockIdx.x * 4L + wave; i < (long)n_items; i += (long)gridDim.x * 4L) {
-                const long r = paired ? i : i / n_t;
-                const long t = paired ? i : i - r * n_t;
-                const double p0 = observer[3 * r], p1 = observer[3 * r + 1], p2 = observer[3 * r + 2];
-                const double d0 = target[3 * t] - p0, d1 = target[3 * t + 1] - p1, d2 = target[3 * t + 2] - p2;
-
-                double best = HUGE_VAL;
-                int best_k = 0, count = 0;
-                for (int k = lane; k < n_f; k += 64) {
-                        const double f = fraction[k];
-                        const double x = p0 + f * d0, y = p1 + f * d1, z = p2 + f * d2;
-                        double la, lo, al, top;
-                        if (FAST) {
-                                f_to_geodetic(x, y, z, la, lo, al);
-                                if ((x != 0.) || (y != 0.)) lo = atan2(y, x) * 180. / kPi;
-                        } else
-                                d_to_geodetic(x, y, z, la, lo, al);
-                        if (!d_layer_top<MODE>(v, ctx, layer, la, lo, top)) continue;
-                        count++;
-                        double g0, g1, g2, e[3], nn[3], u[3];
-                        d_from_geodetic(la, lo, top + 0., g0, g1, g2);
-                        d_enu(la, lo, e, nn, u);
-                        const double c = u[0] * (x - g0) + u[1] * (y - g1) + u[2] * (z - g2);
-                        if (c < best) best = c, best_k = k + 1; /* (a NaN never wins) */
-                }
-                for (int off = 32; off > 0; off >>= 1) {
-                        const double o_best = __shfl_xor(best, off, 64);
-                        const int o_k = __shfl_xor(best_k, off, 64);
-                        count += __shfl_xor(count, off, 64);
-                        /* (a lane without a winner holds (+inf, 0): it never wins, and loses to any) */
-                        if ((o_best < best) || ((o_best == best) && (o_k != 0) && (o_k < best_k)))
-                                best = o_best, best_k = o_k;
-                }
-                if (lane == 0) {
-                        sample[i] = best_k;
-                        if (n_data != nullptr) n_data[i] = count;
-                        if (best_k != 0) clearance[i] = best;
-                }
-        }
-}
-
-__device__ __forceinline__ ull wave_sum(ull v)
-{
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        return v;
-}
-
-/* Add a block's four counters to the global ones: waves -> LDS -> 4 atomics per
- * block.  (One set of atomics per WAVE is what a kernel can least afford: the
- * counters share a cache line, same-line atomics complete at ~5 ns apiece, and
- * the step kernel's 8 192 waves spent 4x their run time queueing there.) */
-__device__ __forceinline__ void block_tally(ull * __restrict__ stats, ull a, ull b, ull c, ull d)
-{
-        __shared__ ull part[4][4]; /* [wave][counter]: blocks are 256 threads */
-        a = wave_sum(a), b = wave_sum(b), c = wave_sum(c), d = wave_sum(d);
-        const int wave = (int)(threadIdx.x >> 6);
-        if ((threadIdx.x & 63) == 0) part[wave][0] = a, part[wave][1] = b, part[wave][2] = c, part[wave][3] = d;
-        __syncthreads();
-        if (threadIdx.x < 4) {
-                const ull sum = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] +
-                    part[3][threadIdx.x];
-                if (sum != 0) atomicAdd(&stats[threadIdx.x], sum);
-        }
-}
 
 /* Where a batch of single steps takes its directions from: an array, or -- a
  * scattering walk (turtle_stepper_scatter_n) -- Philox(first + ray, stream; seed)
@@ -1062,7 +381,6 @@ __global__ void __launch_bounds__(256) k_bisect(tamd_view v, double * __restrict
 
 /* ---- the hot kernel ---------------------------------------------------- */
 
-constexpr int kChunk = 64; /* rays a wave draws from the global queue at once */
 #ifndef PAGED_REFILL
 #define PAGED_REFILL 24
 #endif
@@ -2683,477 +2001,21 @@ __global__ void __launch_bounds__(256) WALK_WAVES_ATTR k_walk(tamd_view v, long 
         block_tally(stats, my_rays, my_steps, my_samples, my_plain);
 }
 
-/* ---- a line of sight per ray ------------------------------------------------
- *
- * turtle_stepper_traverse_n over a geometry with every tile resident: the loop
- * of examples/example-stepper.c:128-140 [ref], one ray per lane from its origin
- * sample to its last step.  k_walk's state machine (one sample per live lane and
- * trip, STEP and BISECT bookkeeping as selects, the crossing located by halving
- * and the ray going on in the new medium from the bisection's last sample) with
- * a fixed direction, a third state for the origin sample (ST_INIT: q = B), the
- * ceiling compared with the altitude turtle_stepper_step publishes (the step's
- * sample after an accepted step, b_alt after a located crossing), and the path
- * summed per medium: the running sum of the medium the ray is in is kept in a
- * register, stored to length[m][r] when a crossing is located and the new
- * medium's total loaded from length[m'][r] -- one load and one store a crossing,
- * the reference's order of additions, and registers independent of the number
- * of media.  Every lane ends through max_steps, the halving guard or the queue
- * running dry.
- * The kernel keeps its OWN copy of the refill loop (queue_refill) and of the select block
- * (step_or_bisect, turtle_amd_device.h), expression for expression: built on the shared ones its
- * 12 instances kept their resources and their results, but scripts/exp_traverse.py measured
- * three of four figures outside the margin (profiles/step_machine_ab.txt).  A change to either
- * has to be made here too; tests/test_gpu_device_api.py and test_gpu_step_machine.py hold this
- * copy to Stepping::trip(), which runs the shared one, bit for bit. */
-struct TraverseIO {
-        const double * __restrict__ dir;
-        double * __restrict__ length; /* [media][n], zeroed by the driver; or NULL */
-        int * __restrict__ n_steps;   /* or NULL */
-        int * __restrict__ n_cross;   /* or NULL */
-        double ceiling;
-        int max_steps;
-};
-
-/* REC (turtle_stepper_crossings_n): one more register, the ray's total path `tot`, summed as len
- * is (an accepted step's ds, a located crossing's ds + ds1), and each located crossing stored into
- * slot `crossings` of the [capacity][n] arrays (the new position, tot, {m, bm}) before the count
- * goes up.  Nothing else changes: the same decisions and additions, the same bits as REC = false,
- * whose instances take an empty last argument. */
-struct NoCrossings {};
-template <bool REC> struct CrossingsArg { typedef NoCrossings type; };
-template <> struct CrossingsArg<true> { typedef tamd_crossings type; };
-
-template <int MODE, bool FAST, bool REC>
-__global__ void __launch_bounds__(256) k_traverse(tamd_view v, long n, double * __restrict__ pos,
-    int * __restrict__ index, TraverseIO io, ull * __restrict__ stats, ull * __restrict__ queue,
-    typename CrossingsArg<REC>::type rec)
-{
-        long pool_next = 0, pool_end = 0; /* wave-uniform */
-        bool exhausted = false;            /* wave-uniform */
-        OneCtx ctx;
-        d_load_ctx<MODE, FAST>(v, ctx);
-        CellCache cell = { ~0u, 0u, 0u, -1, nullptr };
-        CellCache * cache = (FAST && (MODE != TAMD_MODE_GENERIC)) ? &cell : nullptr;
-
-        long ray = -1;
-        bool dead = false;
-        int state = ST_INIT, count = 0, crossings = 0;
-        double bx = 0, by = 0, bz = 0, dx = 0, dy = 0, dz = 0, len = 0;
-        double tot = 0; /* (REC) the path since the origin */
-        double ds = 0, ds0 = 0, ds1 = 0;
-        double s_alt = 0, s_e0 = 0, s_e1 = 0; /* the sample the ray stands on */
-        double b_alt = 0, b_e0 = 0, b_e1 = 0; /* the bisection's last sample of the new medium */
-        int m = -1, k = -1, bm = -1, bk = -1, halvings = 0;
-        ull my_rays = 0, my_steps = 0, my_samples = 0, my_capped = 0;
-
-        for (;;) {
-                /* ---- refill idle lanes from the queue (queue_refill's loop, spelt out) ---- */
-                for (;;) {
-                        const bool need = (ray < 0) && !dead;
-                        const ull mask = __ballot(need);
-                        if (mask == 0) break;
-                        if (pool_next >= pool_end) {
-                                if (exhausted) {
-                                        if (need) dead = true;
-                                        break;
-                                }
-                                ull base = 0;
-                                if ((threadIdx.x & 63) == 0) base = atomicAdd(queue, (ull)kChunk);
-                                base = __shfl(base, 0, 64);
-                                pool_next = (long)base;
-                                pool_end = min((long)base + kChunk, n);
-                                if ((long)base >= n) {
-                                        exhausted = true;
-                                        pool_next = pool_end = 0;
-                                }
-                                continue;
-                        }
-                        const long avail = pool_end - pool_next;
-                        const int rank = lane_rank(mask);
-                        if (need && (rank < avail)) {
-                                ray = pool_next + rank;
-                                bx = pos[3 * ray], by = pos[3 * ray + 1], bz = pos[3 * ray + 2];
-                                dx = io.dir[3 * ray], dy = io.dir[3 * ray + 1], dz = io.dir[3 * ray + 2];
-                                state = ST_INIT, count = 0, crossings = 0, len = 0.;
-                                if constexpr (REC) tot = 0.;
-                        }
-                        pool_next += min((long)__popcll(mask), avail);
-                }
-                if (__ballot(ray >= 0) == 0) break; /* (a lane that drew nothing is dead: so are all) */
-                if (ray >= 0) {
-                        /* ---- one sample at q = B + d * t (the origin itself first) ---- */
-                        const bool init = (state == ST_INIT);
-                        const bool stepping = (state == ST_STEP);
-                        const double t = stepping ? ds : 0.5 * (ds0 + ds1);
-                        const double qx = init ? bx : bx + dx * t, qy = init ? by : by + dy * t,
-                                     qz = init ? bz : bz + dz * t;
-                        Sample s;
-                        d_sample<MODE, FAST>(v, ctx, qx, qy, qz, s, cache);
-                        my_samples++;
-                        bool ended = false;
-                        if (init) { /* [ref stepper.c:780-796] the loop's first call */
-                                m = s.m, k = s.k;
-                                s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
-                                state = ST_STEP;
-                                ended = true;
-                        } else {
-                                /* ---- bookkeeping: step_or_bisect()'s selects, spelt out ---- */
-                                const bool same = (s.m == m);
-                                const bool accept = stepping & same;
-                                const bool cross = stepping & !same;
-                                const bool other = !same;
-                                bx = stepping ? qx : bx, by = stepping ? qy : by, bz = stepping ? qz : bz;
-                                bm = other ? s.m : bm, bk = other ? s.k : bk;
-                                b_alt = other ? s.alt : b_alt, b_e0 = other ? s.e0 : b_e0, b_e1 = other ? s.e1 : b_e1;
-                                ds0 = cross ? -ds : ((!stepping & same) ? t : ds0);
-                                ds1 = cross ? 0. : ((!stepping & other) ? t : ds1);
-                                halvings = stepping ? 0 : halvings + 1;
-                                state = cross ? ST_BISECT : state;
-                                my_steps += stepping ? 1 : 0;
-                                const bool located = (state == ST_BISECT) & !cross &
-                                    (!(ds1 - ds0 > 1E-08) | (halvings > 1200));
-                                ended = accept;
-                                if (accept) {
-                                        len += ds, k = s.k;
-                                        s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
-                                        if constexpr (REC) tot += ds;
-                                }
-                                if (located) { /* [ref stepper.c:861-863] */
-                                        bx = bx + dx * ds1, by = by + dy * ds1, bz = bz + dz * ds1;
-                                        len += ds + ds1;
-                                        if constexpr (REC) {
-                                                tot += ds + ds1;
-                                                if (crossings < rec.capacity) { /* slot [crossings][ray] */
-                                                        const long c = (long)crossings * n + ray;
-                                                        if (rec.point != nullptr)
-                                                                rec.point[3 * c] = bx, rec.point[3 * c + 1] = by,
-                                                                rec.point[3 * c + 2] = bz;
-                                                        if (rec.distance != nullptr) rec.distance[c] = tot;
-                                                        if (rec.media != nullptr)
-                                                                rec.media[2 * c] = m, rec.media[2 * c + 1] = bm;
-                                                }
-                                        }
-                                        /* the sum of the medium left goes out, the new one's comes in */
-                                        if (io.length != nullptr) {
-                                                io.length[(long)m * n + ray] = len;
-                                                len = (bm >= 0) ? io.length[(long)bm * n + ray] : 0.;
-                                        }
-                                        m = bm, k = bk;
-                                        s_alt = b_alt, s_e0 = b_e0, s_e1 = b_e1;
-                                        crossings++;
-                                        state = ST_STEP;
-                                        ended = true;
-                                }
-                                count += ended ? 1 : 0;
-                        }
-                        if (ended) { /* a step is over (or the origin sampled): the loop's test */
-                                const bool low = (m >= 0) && (s_alt < io.ceiling);
-                                if (!low || (count >= io.max_steps)) {
-                                        pos[3 * ray] = bx, pos[3 * ray + 1] = by, pos[3 * ray + 2] = bz;
-                                        index[2 * ray] = m, index[2 * ray + 1] = k;
-                                        if ((io.length != nullptr) && (m >= 0)) io.length[(long)m * n + ray] = len;
-                                        if (io.n_steps != nullptr) io.n_steps[ray] = count;
-                                        if (io.n_cross != nullptr) io.n_cross[ray] = crossings;
-                                        my_rays++;
-                                        my_capped += low ? 1 : 0;
-                                        ray = -1;
-                                } else {
-                                        ds = d_step_length(v, s_alt, s_e0, s_e1, m);
-                                }
-                        }
-                }
-        }
-        block_tally(stats, my_rays, my_steps, my_samples, my_capped);
-}
-
-/* ---- a ray advanced by a column-depth budget ----------------------------------
- *
- * turtle_stepper_advance_n over a geometry with every tile resident: traverse_n's
- * loop (include/turtle_amd.h states it), one ray per lane, with two more ways to
- * end: the column depth X = sum of density[medium] x step has reached the ray's
- * budget B, or the path d its limit M.  Built on the shared machine as k_walk is
- * (queue_refill, step_or_bisect), with k_traverse's third state for the origin
- * sample.  An EVENT is an accepted step or a located crossing: there, and only
- * there, the lane does the definition's bookkeeping with the density of the medium
- * the step started in (read from density[] when the ray enters a medium: a load at
- * every step sat on each lane's chain); while it halves a crossing
- * nothing is tested, and the step's full length ds + ds1 is one value
- * (k_traverse<REC>'s tot += ds + ds1: the same bits).  A step that would reach B or
- * M is cut short: the ray ends at p0 + dir * f, p0 the position the step began at.
- * A lane keeps X, d, B, M and that density over what a k_traverse lane keeps; p0
- * costs nothing: for an accepted step it is the trip's own starting point, and
- * while a crossing is halved it lies in the registers of the sample the ray stood
- * on, which is dead by then.  The tests after an event are traverse's in
- * traverse's order with the two budget tests between them; with B = inf and no M
- * they never fire: the bits of k_traverse.
- *
- * LAW (turtle_stepper_advance_exp_n with scale heights): the density of medium m at
- * altitude h is density[m] * exp(-h / scale_height[m]), the altitude taken as linear
- * in the path within a step.  A LAW lane keeps two values more: ih, the reciprocal of
- * its medium's scale height (0: the medium is uniform), read with rho when the ray
- * enters a medium; and a0, the altitude its step began at, for the time a crossing is
- * halved (s_alt holds p0x then; for an accepted step a0 is still in s_alt at the
- * event).  exp, expm1 and log1p run at events only, the plain double-precision
- * functions in either arithmetic, and a lane whose medium is uniform branches past
- * them: its bits are those of the instance without the law.  The step's depth and its
- * inverse are turtle_amd_device.h's column_depth and column_reach.
- *
- * GRID (turtle_stepper_advance_grid_n): inside a box of voxels the density of ONE
- * medium is the voxel's.  At an event a lane whose medium is the grid's walks the
- * step's segment p0 + dir * [0, L] voxel by voxel (turtle_amd_device.h's grid_depth:
- * the one copy of the arithmetic), L being the step's length or what the distance
- * limit leaves of it; the walk itself stops where the budget runs out, so the far
- * cut and the depth cut come out of one walk.  p0 is where the kernel keeps it
- * anyway (above).  A lane in another medium branches past the walk inside
- * grid_depth: one piece at rho.  The grid's scalars ride in the kernel argument
- * (scalar registers); the voxel loads are the only new memory traffic.  The walk's
- * state lives inside the event only. */
-struct AdvanceIO {
-        const double * __restrict__ dir;
-        const double * __restrict__ density;  /* [media] */
-        const double * __restrict__ budget;   /* [n] */
-        const double * __restrict__ dist_max; /* [n] or NULL */
-        double * __restrict__ depth;          /* or NULL */
-        double * __restrict__ distance;       /* or NULL */
-        int * __restrict__ n_steps;           /* or NULL */
-        int * __restrict__ status;
-        double ceiling;
-        int max_steps;
-};
-struct AdvanceLawIO : AdvanceIO {
-        const double * __restrict__ scale_height; /* [media] */
-};
-struct AdvanceGridIO : AdvanceIO {
-        turtle_amd_grid_view grid;
-};
-
-/* what a LAW lane keeps of its medium's scale height H: 1 / H, and 0 for the uniform H = HUGE_VAL */
-__device__ __forceinline__ double d_inverse_scale(double H) { return (H == HUGE_VAL) ? 0. : 1. / H; }
-
-template <int MODE, bool FAST, bool LAW = false, bool GRID = false>
-__global__ void __launch_bounds__(256) k_advance(tamd_view v, long n, double * __restrict__ pos,
-    int * __restrict__ index,
-    std::conditional_t<GRID, AdvanceGridIO, std::conditional_t<LAW, AdvanceLawIO, AdvanceIO>> io,
-    ull * __restrict__ stats, ull * __restrict__ queue)
-{
-        static_assert(!(LAW && GRID), "a grid together with scale heights is not offered");
-        RayQueue q;
-        OneCtx ctx;
-        d_load_ctx<MODE, FAST>(v, ctx);
-        CellCache cell = { ~0u, 0u, 0u, -1, nullptr };
-        CellCache * cache = (FAST && (MODE != TAMD_MODE_GENERIC)) ? &cell : nullptr;
-
-        long ray = -1;
-        bool dead = false;
-        int state = ST_INIT, count = 0;
-        double bx = 0, by = 0, bz = 0, dx = 0, dy = 0, dz = 0;
-        double X = 0, d = 0, B = 0, M = 0;
-        double rho = 0; /* density[m]: read when the ray enters a medium, not at every step */
-        double ih = 0, a0 = 0; /* (LAW) 1 / scale_height[m], or 0: uniform; the altitude a halved step began at */
-        double ds = 0;
-        /* the sample the ray stands on -- and, while it halves a crossing (ds is set, the sample
-         * no longer needed: an event replaces it), the position p0 its step began at */
-        double s_alt = 0, s_e0 = 0, s_e1 = 0;
-        Bisection b = { 0., 0., 0., 0., 0., -1, -1, 0 };
-        int m = -1, k = -1;
-        ull my_rays = 0, my_steps = 0, my_samples = 0, my_capped = 0;
-
-        for (;;) {
-                queue_refill(q, queue, kChunk, n, ray, dead, [&] {
-                        bx = pos[3 * ray], by = pos[3 * ray + 1], bz = pos[3 * ray + 2];
-                        dx = io.dir[3 * ray], dy = io.dir[3 * ray + 1], dz = io.dir[3 * ray + 2];
-                        B = io.budget[ray];
-                        M = (io.dist_max != nullptr) ? io.dist_max[ray] : HUGE_VAL;
-                        state = ST_INIT, count = 0, X = 0., d = 0.;
-                });
-                if (__ballot(ray >= 0) == 0) break; /* (a lane that drew nothing is dead: so are all) */
-                if (ray >= 0) {
-                        /* ---- one sample at q = B + d * t (the origin itself first) ---- */
-                        const bool init = (state == ST_INIT);
-                        const bool stepping = (state == ST_STEP);
-                        const double t = stepping ? ds : 0.5 * (b.ds0 + b.ds1);
-                        const double qx = init ? bx : bx + dx * t, qy = init ? by : by + dy * t,
-                                     qz = init ? bz : bz + dz * t;
-                        Sample s;
-                        d_sample<MODE, FAST>(v, ctx, qx, qy, qz, s, cache);
-                        my_samples++;
-                        bool event = false;
-                        int status = -1; /* set: the ray ends */
-                        if (init) { /* [ref stepper.c:780-796] the loop's first call */
-                                m = s.m, k = s.k;
-                                s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
-                                if (m >= 0) rho = io.density[m];
-                                if constexpr (LAW) {
-                                        if (m >= 0) ih = d_inverse_scale(io.scale_height[m]);
-                                }
-                                state = ST_STEP;
-                                event = true;
-                        } else {
-                                /* ---- bookkeeping: the step machine of turtle_amd_device.h ---- */
-                                const double ox = bx, oy = by, oz = bz; /* (stepping: where the step begins) */
-                                const StepOutcome o = step_or_bisect(b, state, bx, by, bz, m, ds, t, qx, qy, qz, s);
-                                my_steps += stepping ? 1 : 0;
-                                event = o.accept | o.located;
-                                if constexpr (LAW) {
-                                        if (stepping & !o.accept) a0 = s_alt;
-                                }
-                                if (stepping & !o.accept) s_alt = ox, s_e0 = oy, s_e1 = oz; /* p0, kept for the halving */
-                                if (event) {
-                                        const double p0x = o.accept ? ox : s_alt, p0y = o.accept ? oy : s_e0,
-                                                     p0z = o.accept ? oz : s_e1;
-                                        /* the step's full length, in the medium m it started in */
-                                        const double len = o.located ? ds + b.ds1 : ds;
-                                        double x = rho * len;
-                                        double c = rho, w = 0.; /* the step's law: column_depth(c, w, f) */
-                                        if constexpr (LAW) {
-                                                if (ih != 0.) {
-                                                        const double h0 = o.accept ? s_alt : a0;
-                                                        const double h1 = o.accept ? s.alt : b.b_alt;
-                                                        c = rho * exp(-h0 * ih);
-                                                        w = -((h1 - h0) * ih) / len;
-                                                        x = column_depth(c, w, len);
-                                                }
-                                        }
-                                        GridDepth walk = { 0., 0., false };
-                                        if constexpr (GRID) {
-                                                /* one walk over what the limit leaves of the step: its depth, or where
-                                                 * the budget runs out inside it (walk.f: there, or the whole of L) */
-                                                double L = (d + len >= M) ? M - d : len;
-                                                if (L > len) L = len;
-                                                walk = grid_depth(io.grid, rho, m, p0x, p0y, p0z, dx, dy, dz, L, B - X);
-                                                x = walk.x;
-                                        }
-                                        const bool spent = GRID ? walk.stopped : (X + x >= B), far = (d + len >= M);
-                                        count++;
-                                        if (spent | far) { /* the step is cut short, inside medium m */
-                                                if constexpr (GRID) {
-                                                        const double f = walk.f;
-                                                        status = spent ? TURTLE_AMD_ADVANCE_SPENT : TURTLE_AMD_ADVANCE_DISTANCE;
-                                                        bx = p0x + dx * f, by = p0y + dy * f, bz = p0z + dz * f;
-                                                        X = spent ? B : X + x;
-                                                        d = spent ? d + f : M;
-                                                } else {
-                                                        double f = far ? M - d : len;
-                                                        status = far ? TURTLE_AMD_ADVANCE_DISTANCE : TURTLE_AMD_ADVANCE_SPENT;
-                                                        if (spent) {
-                                                                const double fs = LAW ? column_reach(c, w, B - X) : (B - X) / rho;
-                                                                if (fs <= f) f = fs, status = TURTLE_AMD_ADVANCE_SPENT;
-                                                        }
-                                                        if (f > len) f = len; /* (a rounding guard) */
-                                                        bx = p0x + dx * f, by = p0y + dy * f, bz = p0z + dz * f;
-                                                        const bool by_depth = (status == TURTLE_AMD_ADVANCE_SPENT);
-                                                        X = by_depth ? B : X + (LAW ? column_depth(c, w, f) : rho * f);
-                                                        d = by_depth ? d + f : M;
-                                                }
-                                        } else {
-                                                X += x, d += len;
-                                                if (o.accept) {
-                                                        k = s.k;
-                                                        s_alt = s.alt, s_e0 = s.e0, s_e1 = s.e1;
-                                                } else { /* [ref stepper.c:861-863] */
-                                                        bx = bx + dx * b.ds1, by = by + dy * b.ds1, bz = bz + dz * b.ds1;
-                                                        m = b.bm, k = b.bk;
-                                                        s_alt = b.b_alt, s_e0 = b.b_e0, s_e1 = b.b_e1;
-                                                        if (m >= 0) rho = io.density[m];
-                                                        if constexpr (LAW) {
-                                                                if (m >= 0) ih = d_inverse_scale(io.scale_height[m]);
-                                                        }
-                                                }
-                                        }
-                                        state = ST_STEP;
-                                }
-                        }
-                        if (event) { /* a step is over (or the origin sampled): the loop's tests */
-                                if (status < 0) {
-                                        if (m < 0) status = TURTLE_AMD_ADVANCE_LEFT;
-                                        else if (!(X < B)) status = TURTLE_AMD_ADVANCE_SPENT;
-                                        else if (!(d < M)) status = TURTLE_AMD_ADVANCE_DISTANCE;
-                                        /* (s_alt, s_e0, s_e1: after an event always the sample again, never p0) */
-                                        else if (!(s_alt < io.ceiling)) status = TURTLE_AMD_ADVANCE_CEILING;
-                                        else if (count >= io.max_steps) status = TURTLE_AMD_ADVANCE_MAX_STEPS;
-                                }
-                                if (status >= 0) {
-                                        pos[3 * ray] = bx, pos[3 * ray + 1] = by, pos[3 * ray + 2] = bz;
-                                        index[2 * ray] = m, index[2 * ray + 1] = k;
-                                        if (io.depth != nullptr) io.depth[ray] = X;
-                                        if (io.distance != nullptr) io.distance[ray] = d;
-                                        if (io.n_steps != nullptr) io.n_steps[ray] = count;
-                                        io.status[ray] = status;
-                                        my_rays++;
-                                        my_capped += (status == TURTLE_AMD_ADVANCE_MAX_STEPS) ? 1 : 0;
-                                        ray = -1;
-                                } else {
-                                        ds = d_step_length(v, s_alt, s_e0, s_e1, m);
-                                }
-                        }
-                }
-        }
-        block_tally(stats, my_rays, my_steps, my_samples, my_capped);
-}
-
-/* After one generation of a paged traverse (or, `first`, after the origins were
- * sampled): the step each live ray took added to the sum of the medium it
- * started in, the loop's test, and the rays it ends taken out of the stepping
- * (live_index[r][0] = -1; their results are in index).  medium[r]: the medium a
- * live ray is in, -1 once it is done. */
-__global__ void k_traverse_gen(long n, int first, const double * __restrict__ alt,
-    const double * __restrict__ step, int * __restrict__ live_index, int * __restrict__ medium,
-    int * __restrict__ index, double * __restrict__ length, int * __restrict__ n_steps,
-    int * __restrict__ n_cross, double ceiling, int max_steps, ull * __restrict__ counters)
-{
-        ull my_rays = 0, my_steps = 0, my_capped = 0, my_live = 0;
-        for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
-             r += (long)gridDim.x * blockDim.x) {
-                const int m1 = live_index[2 * r];
-                int count = 0;
-                if (first) {
-                        n_steps[r] = 0, n_cross[r] = 0;
-                } else {
-                        const int m0 = medium[r];
-                        if (m0 < 0) continue; /* done earlier */
-                        if (length != nullptr) length[(long)m0 * n + r] += step[r];
-                        count = n_steps[r] + 1;
-                        n_steps[r] = count;
-                        n_cross[r] += (m1 != m0) ? 1 : 0;
-                        my_steps++;
-                }
-                index[2 * r] = m1, index[2 * r + 1] = live_index[2 * r + 1];
-                const bool low = (m1 >= 0) && (alt[r] < ceiling);
-                if (!low || (count >= max_steps)) {
-                        medium[r] = -1, live_index[2 * r] = -1;
-                        my_rays++;
-                        my_capped += low ? 1 : 0;
-                } else {
-                        medium[r] = m1;
-                        my_live++;
-                }
-        }
-        block_tally(counters, my_rays, my_steps, my_capped, my_live);
-}
-
-/* A paged turtle_stepper_crossings_n, after a generation's steps and before its k_traverse_gen
- * (which still holds the medium each live ray started in, and its crossing count): the step added
- * to the ray's running total, and a ray whose medium changed (m1 != m0) records its new position,
- * that total and {m0, m1} in slot n_cross[r].  k_traverse<REC>'s additions: the same bits. */
-__global__ void k_crossings_gen(long n, const double * __restrict__ pos, const double * __restrict__ step,
-    const int * __restrict__ live_index, const int * __restrict__ medium, const int * __restrict__ n_cross,
-    double * __restrict__ total, tamd_crossings rec)
+/* Batch map projections.  By its subject a kernel of points.hip; it is here for d_project, which
+ * is not inlined: a unit's one copy of it is compiled for the widest block among the kernels that
+ * call it there, and only this kernel, of 1 024 threads a block at the most, gives the copy that the
+ * trace and step kernels call the registers it has always had. */
+__global__ void k_project(tamd_proj pr, int inverse, long n, const double * __restrict__ a,
+    const double * __restrict__ b, double * __restrict__ c, double * __restrict__ d)
 {
         for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n;
              r += (long)gridDim.x * blockDim.x) {
-                const int m0 = medium[r];
-                if (m0 < 0) continue; /* done earlier */
-                const double tot = total[r] + step[r];
-                total[r] = tot;
-                const int m1 = live_index[2 * r];
-                if ((m1 != m0) && (n_cross[r] < rec.capacity)) {
-                        const long c = (long)n_cross[r] * n + r;
-                        if (rec.point != nullptr)
-                                rec.point[3 * c] = pos[3 * r], rec.point[3 * c + 1] = pos[3 * r + 1],
-                                rec.point[3 * c + 2] = pos[3 * r + 2];
-                        if (rec.distance != nullptr) rec.distance[c] = tot;
-                        if (rec.media != nullptr) rec.media[2 * c] = m0, rec.media[2 * c + 1] = m1;
-                }
+                double u, w;
+                if (inverse)
+                        d_unproject(pr, a[r], b[r], u, w);
+                else
+                        d_project(pr, a[r], b[r], u, w);
+                c[r] = u, d[r] = w;
         }
 }
 
@@ -3337,240 +2199,11 @@ __global__ void __launch_bounds__(kOrderThreads) k_order_place(long n, const uns
         });
 }
 
-/* ---- turtle_map_resample ------------------------------------------------------
- * Every node of a target map filled from a stack or another map: the loop of the
- * reference's examples/example-projection.c (turtle_map_node, _unproject,
- * turtle_stack_elevation, turtle_map_fill) in one launch.  One WAVE per 8 x 8 block of
- * the target, its 64 lanes the block's 64 nodes in the HBM order (internal.h): the
- * wave's store of the new codes is one 128-byte line, and neighbouring lanes look up
- * neighbouring source cells.  The kernel writes a whole new copy of the target in that
- * layout; a node that stays as it is (outside the data, or outside the map's span
- * without TURTLE_AMD_RESAMPLE_CLAMP) gets the code of the map's current copy, so that a
- * block's work can be done again and the copy is complete whatever the host decides.
- * Lookups are the strict bilinear ones of k_elevation: the result does not depend on
- * the arithmetic mode. */
-enum { RS_STACK = 0, RS_MAP = 1 };
-
-/* page_fault for an item that is a whole wave (a target block): the block is listed
- * once if any of its nodes met a tile that is not resident, and is redone whole in a
- * later round; each tile it wants counts once per block (the usual case: one tile), a
- * seam's neighbours once per node that wants them */
-__device__ __forceinline__ void page_fault_block(const Paging & pg, const TileFault & f, int item)
-{
-        const bool fault = f.centre >= 0;
-        const ull mask = __ballot(fault);
-        if (mask == 0) return;
-        const int lane = (int)(threadIdx.x & 63);
-        const int leader = __builtin_ctzll(mask);
-        ull base = 0;
-        if (lane == leader) {
-                base = atomicAdd(pg.n_faulted, 1ull);
-                pg.faulted[base] = item;
-        }
-        base = __shfl(base, leader, 64);
-        const bool first = (pg.first_id >= 0) ? (item == pg.first_id) : (base == 0);
-        if (fault) {
-                for (int b = 0; b < 9; b++) {
-                        if (!((f.mask >> b) & 1)) continue;
-                        const int t = f.centre + (b / 3 - 1) * f.stride + (b % 3 - 1);
-                        if (b != 4) atomicAdd(&pg.wanted[(size_t)t * TAMD_DEMAND_STRIDE], 1u);
-                        if (first) atomicOr(&pg.wanted_first[t >> 5], 1u << (t & 31));
-                }
-        }
-        const bool centre = fault && (((f.mask >> 4) & 1) != 0);
-        ull left = __ballot(centre);
-        while (left != 0) {
-                const int lead = __builtin_ctzll(left);
-                const int t0 = __shfl(f.centre, lead, 64);
-                const ull same = __ballot(centre && (f.centre == t0));
-                if (lane == lead) atomicAdd(&pg.wanted[(size_t)t0 * TAMD_DEMAND_STRIDE], 1u);
-                left &= ~same;
-        }
-}
-
-/* grids[0]: the target (nodes: its current HBM copy; x0 .. dy, nbx and proj as the
- * map holds them); grids[1]: the source map (RS_MAP).  z0, dz, is_signed: the
- * target's own encoding, as turtle_map_fill applies it.  counters (zeroed by the
- * caller, added to round after round): nodes outside the data, nodes outside the span
- * and not clamped, nodes clamped.  Items are the target's blocks; over a paged stack,
- * a block with a faulting node is listed and none of its work is kept. */
-template <int SRC, int TPROJ /* the target's projection type */>
-__global__ void __launch_bounds__(256) k_resample(tamd_view v, const tamd_grid * __restrict__ grids,
-    double z0, double dz, int is_signed, int flags, long n_blocks, uint16_t * __restrict__ out, Paging pg,
-    ull * __restrict__ counters)
-{
-        const tamd_grid & t = grids[0];
-        const int lane = (int)(threadIdx.x & 63);
-        const long waves = (long)gridDim.x * (blockDim.x >> 6);
-        const long n_items = (pg.n_in != nullptr) ? (long)*pg.n_in : n_blocks;
-        const double top = z0 + 65535 * dz; /* [ref map.c:196-197] */
-        ull n_outside = 0, n_bad = 0, n_clamped = 0;
-        for (long i = blockIdx.x * (long)(blockDim.x >> 6) + (threadIdx.x >> 6); i < n_items; i += waves) {
-                const long blk = (pg.ids != nullptr) ? (long)pg.ids[i] : i;
-                const int ix = (int)(blk % t.nbx) * TAMD_BLOCK + (lane & 7);
-                const int iy = (int)(blk / t.nbx) * TAMD_BLOCK + (lane >> 3);
-                TileFault f = { -1, 0, 0 };
-                bool keep = true;
-                int outside = 0, bad = 0, clamped = 0;
-                uint16_t code = 0;
-                if ((ix < t.nx) && (iy < t.ny)) {
-                        /* turtle_map_node [ref map.c:217-218] */
-                        const double x = t.x0 + ix * t.dx;
-                        const double y = t.y0 + iy * t.dy;
-                        double latitude, longitude;
-                        if (TPROJ >= 0)
-                                d_unproject_body<TPROJ>(t.proj, x, y, latitude, longitude);
-                        else
-                                latitude = y, longitude = x;
-                        double z = 0.;
-                        int in;
-                        if (SRC == RS_STACK) {
-                                in = d_stack_elevation<false>(v, v.stacks[0], latitude, longitude, z, f);
-                                if (in >= 0) f.centre = -1;
-                        } else {
-                                const tamd_grid & s = grids[1];
-                                double u, w;
-                                if (flags & TAMD_RESAMPLE_IDENTITY)
-                                        u = x, w = y;
-                                else if (s.proj.type >= 0)
-                                        d_project_body(s.proj, latitude, longitude, u, w);
-                                else
-                                        u = longitude, w = latitude;
-                                in = d_grid_elevation<false>(s, u, w, z) ? 1 : 0;
-                        }
-                        if (in == 0) {
-                                outside = 1;
-                        } else if (in > 0) {
-                                /* turtle_map_fill [ref map.c:192-200, :47-51] */
-                                const bool off = ((dz <= 0.) && (z != z0)) || (z < z0) || (z > top);
-                                if (off && !(flags & TURTLE_AMD_RESAMPLE_CLAMP)) {
-                                        bad = 1;
-                                } else {
-                                        if (off) {
-                                                clamped = 1;
-                                                z = ((dz <= 0.) || (z < z0)) ? z0 : top;
-                                        }
-                                        if (is_signed)
-                                                code = (uint16_t)(int)z; /* (int16)z */
-                                        else
-                                                code = (dz > 0.) ? (uint16_t)(unsigned)round((z - z0) / dz) : 0;
-                                        keep = false;
-                                }
-                        }
-                }
-                if (pg.faulted != nullptr) {
-                        const bool redo = __ballot(f.centre >= 0) != 0;
-                        page_fault_block(pg, f, (int)blk);
-                        if (redo) continue; /* (the whole wave) */
-                }
-                const size_t k = (size_t)blk * 64 + lane;
-                if (keep) code = GLOBAL_NODES(t.nodes)[k];
-                out[k] = code;
-                n_outside += outside, n_bad += bad, n_clamped += clamped;
-        }
-        block_tally(counters, n_outside, n_bad, n_clamped, 0);
-}
-
-/* The host copy of a map from its HBM copy: rows of nx nodes, south to north */
-__global__ void k_unblock(const uint16_t * __restrict__ blocked, int nx, int ny, int nbx,
-    uint16_t * __restrict__ rows)
-{
-        const long n = (long)nx * ny;
-        for (long k = blockIdx.x * (long)blockDim.x + threadIdx.x; k < n; k += (long)gridDim.x * blockDim.x) {
-                const int iy = (int)(k / nx), ix = (int)(k - (long)iy * nx);
-                rows[k] = GLOBAL_NODES(blocked)[d_node_index(nbx, ix, iy)];
-        }
-}
-
-/* turtle_map_fill_n, first half: the window's elevations (row j at z + j * ld) to the codes
- * turtle_map_fill stores, k_resample's expressions in its operand order, into a compact
- * buffer of ny rows of nx codes.  Nothing of the map is written: the host commits
- * (k_fill_store) only after it has read counters[0] == 0.  counters (zeroed by the caller):
- * elements that fail the call, elements clamped, and the failed ones that turtle_map_fill calls
- * "inconsistent" (dz <= 0 and z != z0; a NaN is not among them). */
-__global__ void __launch_bounds__(256) k_fill_encode(const double * __restrict__ z_in, long ld, int nx, long n,
-    double z0, double dz, int is_signed, int flags, uint16_t * __restrict__ codes, ull * __restrict__ counters)
-{
-        const double top = z0 + 65535 * dz; /* [ref map.c:196-197] */
-        ull n_bad = 0, n_clamped = 0, n_inconsistent = 0;
-        for (long k = blockIdx.x * (long)blockDim.x + threadIdx.x; k < n; k += (long)gridDim.x * blockDim.x) {
-                const long j = k / nx;
-                double z = z_in[j * ld + (k - j * nx)];
-                /* turtle_map_fill [ref map.c:192-200, :47-51]; a NaN passes none of its comparisons */
-                const bool nan = (z != z);
-                const bool off = nan || ((dz <= 0.) && (z != z0)) || (z < z0) || (z > top);
-                uint16_t code = 0;
-                if (off && (nan || !(flags & TURTLE_AMD_FILL_CLAMP))) {
-                        n_bad++, n_inconsistent += (!nan && (dz <= 0.) && (z != z0)) ? 1 : 0;
-                } else {
-                        if (off) {
-                                n_clamped++;
-                                z = ((dz <= 0.) || (z < z0)) ? z0 : top;
-                        }
-                        if (is_signed)
-                                code = (uint16_t)(int)z; /* (int16)z */
-                        else
-                                code = (dz > 0.) ? (uint16_t)(unsigned)round((z - z0) / dz) : 0;
-                }
-                codes[k] = code;
-        }
-        block_tally(counters, n_bad, n_clamped, n_inconsistent, 0);
-}
-
-/* ... second half: the codes into the map's HBM copy, in place.  One wave a touched 8 x 8
- * block (nwx of them a row of the window), its lanes in HBM order: a lane outside the window
- * keeps the code that is there (blank: the copy held nothing yet and the window is the whole
- * map -- the padding of its last blocks is zeroed), and the block goes out as its 128-byte line. */
-__global__ void __launch_bounds__(256) k_fill_store(uint16_t * __restrict__ nodes, int nbx, int ix0, int iy0,
-    int nx, int ny, int nwx, long n_blocks, int blank, const uint16_t * __restrict__ codes)
-{
-        const int lane = (int)(threadIdx.x & 63);
-        const long waves = (long)gridDim.x * (blockDim.x >> 6);
-        for (long i = blockIdx.x * (long)(blockDim.x >> 6) + (threadIdx.x >> 6); i < n_blocks; i += waves) {
-                const int bx = (ix0 >> 3) + (int)(i % nwx), by = (iy0 >> 3) + (int)(i / nwx);
-                const int ix = bx * TAMD_BLOCK + (lane & 7) - ix0, iy = by * TAMD_BLOCK + (lane >> 3) - iy0;
-                const size_t k = ((size_t)by * nbx + bx) * 64 + lane;
-                uint16_t code = 0;
-                if ((ix >= 0) && (ix < nx) && (iy >= 0) && (iy < ny))
-                        code = codes[(long)iy * nx + ix];
-                else if (!blank)
-                        code = GLOBAL_NODES(nodes)[k];
-                nodes[k] = code;
-        }
-}
-
-/* turtle_map_node_n: the window's nodes decoded as turtle_map_node decodes them [ref
- * map.c:41-44], row j to out + j * ld; consecutive lanes store consecutive doubles */
-__global__ void __launch_bounds__(256) k_nodes(const uint16_t * __restrict__ nodes, int nbx, int ix0, int iy0,
-    int nx, long n, double z0, double dz, int is_signed, double * __restrict__ out, long ld)
-{
-        for (long k = blockIdx.x * (long)blockDim.x + threadIdx.x; k < n; k += (long)gridDim.x * blockDim.x) {
-                const long j = k / nx;
-                const int i = (int)(k - j * nx);
-                const uint16_t code = GLOBAL_NODES(nodes)[d_node_index(nbx, ix0 + i, iy0 + (int)j)];
-                out[j * ld + i] = is_signed ? (double)(int16_t)code : z0 + code * dz;
-        }
-}
-
 } /* namespace */
 
 /* ======================================================================== */
 /*                             the launch layer                             */
 /* ======================================================================== */
-
-#define g_stream (g_ctx.stream)
-#define g_cus (g_ctx.cus)
-#define g_math_strict (g_ctx.math_strict)
-
-/* Which arithmetic a stepping call runs in.  FAST takes its samples from closed forms and lines that
- * are a few 1e-9 m off the exact transform (kLineTau0): a stepper whose minimum step is below the
- * 1e-8 m of the bisection's bracket asks for steps finer than that noise -- a ray that creeps along
- * the ground then crosses it tens of steps earlier or later than the reference's, or not before
- * max_steps -- and is served by the STRICT kernels whatever the mode (a NaN resolution too). */
-static bool strict_math(const tamd_view & view)
-{
-        return g_math_strict || !view.fast_ok || !(view.resolution >= 1E-08);
-}
 
 #ifdef TRACE_POOL_STATS
 extern "C" int tamd_dev_pool_stats(unsigned long long * out, int reset)
@@ -3583,184 +2216,6 @@ extern "C" int tamd_dev_pool_stats(unsigned long long * out, int reset)
         return 0;
 }
 #endif
-
-static int grid_for(long n, int block)
-{
-        long blocks = (n + block - 1) / block;
-        /* (4, 16 or 64 blocks per CU: the same or worse, measured on the step kernel) */
-        const long cap = (long)(g_cus > 0 ? g_cus : 256) * 8;
-        if (blocks > cap) blocks = cap;
-        if (blocks < 1) blocks = 1;
-        return (int)blocks;
-}
-
-/* `blocks` blocks of 256 threads of a kernel, on the calling thread's stream */
-template <class... P, class... A>
-static int launch_blocks(const char * name, void (*kernel)(P...), unsigned blocks, size_t lds_bytes,
-    const A &... args)
-{
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds_bytes, g_stream, args...);
-        LAUNCH_CHECK(name);
-        return 0;
-}
-/* A whole flat entry point: n items, each the work of one thread (none: nothing to do) */
-template <class... P, class... A>
-static int launch_items(const char * name, void (*kernel)(P...), long n, size_t lds_bytes, const A &... args)
-{
-        if (tamd_dev_init()) return 1;
-        if (n <= 0) return 0;
-        return launch_blocks(name, kernel, grid_for(n, 256), lds_bytes, args...);
-}
-
-/* What a launcher zeroes before its kernels: the first n_stats words of `stats` (0: none, they add
- * up over the rounds of a call) and the first n_queue of `queue`.  A fill is a launch of its own,
- * 5 us between two dependent kernels: the two are ONE where they are neighbours, as in a stepper's
- * d_stats (internal.h: TAMD_STATS_QUEUE). */
-static int zero_words(ull * stats, int n_stats, ull * queue, int n_queue)
-{
-        if ((n_stats > 0) && (queue == stats + TAMD_STATS_QUEUE) && (n_stats <= TAMD_STATS_QUEUE)) {
-                HIP_TRY(hipMemsetAsync(stats, 0, (size_t)(TAMD_STATS_QUEUE + n_queue) * sizeof(ull), g_stream));
-                return 0;
-        }
-        if (n_stats > 0) HIP_TRY(hipMemsetAsync(stats, 0, (size_t)n_stats * sizeof(ull), g_stream));
-        HIP_TRY(hipMemsetAsync(queue, 0, (size_t)n_queue * sizeof(ull), g_stream));
-        return 0;
-}
-
-/* A run-time value that a kernel takes as a template parameter: f is called with the
- * std::integral_constant of the first of VALUES that equals `value`, or of the last. */
-template <int FIRST, int... REST, class F>
-static int with_constant(int value, F && f)
-{
-        if constexpr (sizeof...(REST) > 0)
-                if (value != FIRST) return with_constant<REST...>(value, f);
-        return f(std::integral_constant<int, FIRST>());
-}
-/* ... the geometry's MODE (one map, one stack, else the generic instance) */
-template <class F>
-static int with_mode(int mode, F && f)
-{
-        return with_constant<TAMD_MODE_ONE_MAP, TAMD_MODE_ONE_STACK, TAMD_MODE_GENERIC>(mode, f);
-}
-
-/* ... the arithmetic (Strict, else Fast: a kernel's FAST) */
-typedef std::integral_constant<int, 0> Strict;
-typedef std::integral_constant<int, 1> Fast;
-template <class F>
-static int with_math(bool strict, F && f)
-{
-        return with_constant<Strict::value, Fast::value>(strict ? Strict::value : Fast::value, f);
-}
-
-extern "C" int tamd_k_ecef_from_geodetic(long n, const double * lat,
-    const double * lon, const double * elev, double * ecef)
-{
-        return launch_items("k_ecef_from_geodetic", k_ecef_from_geodetic, n, 0, n, lat, lon, elev, ecef);
-}
-
-extern "C" int tamd_k_ecef_to_geodetic(
-    long n, const double * ecef, double * lat, double * lon, double * alt)
-{
-        return with_math(g_math_strict, [&](auto fast) {
-                return launch_items("k_ecef_to_geodetic", k_ecef_to_geodetic<decltype(fast)::value>, n, 0, n,
-                    ecef, lat, lon, alt);
-        });
-}
-
-extern "C" int tamd_k_ecef_from_horizontal(long n, const double * lat,
-    const double * lon, const double * az, const double * el, double * dir)
-{
-        return launch_items("k_ecef_from_horizontal", k_ecef_from_horizontal, n, 0, n, lat, lon, az, el, dir);
-}
-
-extern "C" int tamd_k_ecef_to_horizontal(long n, const double * lat,
-    const double * lon, const double * dir, double * az, double * el)
-{
-        return launch_items("k_ecef_to_horizontal", k_ecef_to_horizontal, n, 0, n, lat, lon, dir, az, el);
-}
-
-extern "C" int tamd_k_elevation(struct tamd_view view, long n, const double * a,
-    const double * b, double * z, int * inside, struct tamd_paging pg)
-{
-        return launch_items("k_elevation", k_elevation, n, 0, view, n, a, b, z, inside, pg);
-}
-
-extern "C" int tamd_k_project(struct tamd_proj proj, int inverse, long n, const double * a,
-    const double * b, double * c, double * d)
-{
-        return launch_items("k_project", k_project, n, 0, proj, inverse, n, a, b, c, d);
-}
-
-extern "C" int tamd_k_gradient(struct tamd_view view, long n, const double * a,
-    const double * b, double * ga, double * gb, int * inside, struct tamd_paging pg)
-{
-        return launch_items("k_gradient", k_gradient, n, 0, view, n, a, b, ga, gb, inside, pg);
-}
-
-extern "C" int tamd_k_position(struct tamd_view view, long n, const double * lat,
-    const double * lon, const double * height, int layer, double * pos,
-    int * data_index, struct tamd_paging pg)
-{
-        return launch_items("k_position", k_position, n, 0, view, n, lat, lon, height, layer, pos,
-            data_index, pg);
-}
-
-extern "C" int tamd_k_normal(struct tamd_view view, long n, const double * pos, const int * layer,
-    double * normal, int * data_index, struct tamd_paging pg)
-{
-        return with_mode(view.mode, [&](auto mode) {
-                return launch_items("k_normal", k_normal<decltype(mode)::value>, n, 0, view, n, pos, layer,
-                    normal, data_index, pg);
-        });
-}
-
-/* A kernel over n_items = observers x azimuths lines of sight, one wave each, four to a block:
- * `launch(mode, fast, grid)` names the instance and passes its arguments. */
-template <class Launch>
-static int launch_sight(struct tamd_view view, int n_items, int n_azimuths, int n_distances, Launch launch)
-{
-        if (tamd_dev_init()) return 1;
-        if ((n_items <= 0) || (n_azimuths <= 0) || (n_distances <= 0)) return 0;
-        return with_mode(view.mode, [&](auto mode) {
-                return with_math(g_math_strict,
-                    [&](auto fast) { return launch(mode, fast, grid_for(64L * n_items, 256)); });
-        });
-}
-
-extern "C" int tamd_k_horizon(struct tamd_view view, int n_items, int n_azimuths, int n_distances,
-    const double * pos, const double * azimuth, const double * distance, int layer, double * elevation,
-    int * sample, double * range)
-{
-        return launch_sight(view, n_items, n_azimuths, n_distances, [&](auto mode, auto fast, auto grid) {
-                return launch_blocks("k_horizon", k_horizon<decltype(mode)::value, decltype(fast)::value>, grid, 0,
-                    view, n_items, n_azimuths, n_distances, pos, azimuth, distance, layer, elevation, sample, range);
-        });
-}
-
-/* the same lines, every sample of each written: visible [n_items][n_distances] and the rest */
-extern "C" int tamd_k_viewshed(struct tamd_view view, int n_items, int n_azimuths, int n_distances,
-    const double * pos, const double * azimuth, const double * distance, int layer, double target_height,
-    signed char * visible, double * sine, double * horizon, int * n_visible)
-{
-        return launch_sight(view, n_items, n_azimuths, n_distances, [&](auto mode, auto fast, auto grid) {
-                return launch_blocks("k_viewshed", k_viewshed<decltype(mode)::value, decltype(fast)::value>, grid, 0,
-                    view, n_items, n_azimuths, n_distances, pos, azimuth, distance, layer, target_height, visible,
-                    sine, horizon, n_visible);
-        });
-}
-
-/* chords, not fans: n_items lines from observers to targets (item r * n_targets + t, or r alone
- * where paired), the minimum over n_fractions samples of each */
-extern "C" int tamd_k_clearance(struct tamd_view view, int n_items, int n_targets, int paired, int n_fractions,
-    const double * observer, const double * target, const double * fraction, int layer, double * clearance,
-    int * sample, int * n_data)
-{
-        return launch_sight(view, n_items, n_targets, n_fractions, [&](auto mode, auto fast, auto grid) {
-                return launch_blocks("k_clearance", k_clearance<decltype(mode)::value, decltype(fast)::value>, grid, 0,
-                    view, n_items, n_targets, paired, n_fractions, observer, target, fraction, layer, clearance,
-                    sample, n_data);
-        });
-}
 
 /* n single steps: the step kernel, then -- with a direction and scratch for
  * the list -- the bisection of the rays that crossed a boundary.  stats /
@@ -3800,36 +2255,6 @@ extern "C" int tamd_k_step(struct tamd_view view, long n, double * pos,
         const StepWalk no_walk = { 0, 0, 0, 0, nullptr, nullptr };
         return run_step(view, n, pos, dir, lat, lon, alt, elev, step, index, flags, none, pg,
             nullptr, no_walk);
-}
-
-/* Waves per SIMD the trace kernel is launched with.  It is fp64-VALU bound
- * with a dependent 4-node gather per sample, so a few waves per SIMD are
- * enough to cover the gather latency: as many as fit. */
-static int trace_blocks_per_cu(const void * kernel)
-{
-        int blocks = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, 256, 0) !=
-                hipSuccess ||
-            blocks < 1)
-                blocks = 1;
-        /* batches in flight share the SIMDs: a kernel that takes one block a CU fewer than fit
-         * leaves registers for a wave of another batch's kernel beside its own (three C2 batches
-         * in flight: 2.38 -> 2.29 ms a pass over 10 passes, 2.39 -> 2.18 over 20; C4 25.5 -> 24.7;
-         * through a stack no change -- two blocks a CU whatever fits: C2 the same, C4 24.1, but C3
-         * 23.9 -> 25.3; alone a kernel would lose either way: C2 3.55 -> 3.7 with two) */
-        if ((g_ctx.in_flight > 1) && (blocks > 2)) blocks -= 1;
-        return blocks;
-}
-
-/* The grid of a persistent kernel over n rays: the blocks that fit the chip, or that the
- * rays can fill */
-template <class... P>
-static unsigned persistent_blocks(void (*kernel)(P...), long n)
-{
-        long blocks = (long)g_cus * trace_blocks_per_cu((const void *)kernel);
-        const long useful = (n + 255) / 256;
-        if (blocks > useful) blocks = useful;
-        return (unsigned)blocks;
 }
 
 template <int MODE, bool FAST, bool MODEL, bool PAGED, bool CROSS, bool POOL = false>
@@ -4405,75 +2830,6 @@ extern "C" int tamd_k_walk(struct tamd_view view, long n, double * pos, double *
         });
 }
 
-template <int MODE, bool REC>
-static int launch_traverse(const tamd_view & view, long n, double * pos, int * index, const TraverseIO & io,
-    ull * stats, ull * queue, bool strict, typename CrossingsArg<REC>::type rec)
-{
-        return with_math(strict, [&](auto fast) {
-                const auto kernel = k_traverse<MODE, decltype(fast)::value, REC>;
-                return launch_blocks("k_traverse", kernel, persistent_blocks(kernel, n), 0, view, n, pos, index, io,
-                    stats, queue, rec);
-        });
-}
-
-/* A whole traverse in one launch (k_traverse): every tile resident, nothing listed */
-extern "C" int tamd_k_traverse(struct tamd_view view, long n, double * pos, const double * dir,
-    double ceiling, int max_steps, int * index, double * length, int * n_steps, int * n_cross,
-    const struct tamd_crossings * rec, unsigned long long * stats, unsigned long long * queue)
-{
-        if (tamd_dev_init()) return 1;
-        if (zero_words(stats, 4, queue, 1)) return 1;
-        if (n <= 0) return 0;
-        const TraverseIO io = { dir, length, n_steps, n_cross, ceiling, max_steps };
-        const bool strict = strict_math(view);
-        return with_mode(view.mode, [&](auto mode) {
-                constexpr int MODE = decltype(mode)::value;
-                if (rec != nullptr)
-                        return launch_traverse<MODE, true>(view, n, pos, index, io, stats, queue, strict, *rec);
-                return launch_traverse<MODE, false>(view, n, pos, index, io, stats, queue, strict, NoCrossings());
-        });
-}
-
-/* A whole advance in one launch (k_advance): every tile resident, nothing listed.  scale_height
- * NULL: the instances without the law; grid (host memory, its density a device pointer) not NULL:
- * the grid instances */
-extern "C" int tamd_k_advance(struct tamd_view view, long n, double * pos, const double * dir,
-    const double * density, const double * scale_height, const struct turtle_amd_grid_view * grid,
-    const double * budget, const double * distance_max,
-    double ceiling, int max_steps, int * index, double * depth, double * distance, int * n_steps, int * status,
-    unsigned long long * stats, unsigned long long * queue)
-{
-        if (tamd_dev_init()) return 1;
-        if (zero_words(stats, 4, queue, 1)) return 1;
-        if (n <= 0) return 0;
-        const AdvanceIO io = { dir, density, budget, distance_max, depth, distance, n_steps, status, ceiling,
-                max_steps };
-        const bool strict = strict_math(view);
-        return with_mode(view.mode, [&](auto mode) {
-                return with_math(strict, [&](auto fast) {
-                        if (scale_height != nullptr) {
-                                AdvanceLawIO law;
-                                static_cast<AdvanceIO &>(law) = io;
-                                law.scale_height = scale_height;
-                                const auto kernel = k_advance<decltype(mode)::value, decltype(fast)::value, true>;
-                                return launch_blocks("k_advance", kernel, persistent_blocks(kernel, n), 0, view, n,
-                                    pos, index, law, stats, queue);
-                        }
-                        if (grid != nullptr) {
-                                AdvanceGridIO g;
-                                static_cast<AdvanceIO &>(g) = io;
-                                g.grid = *grid;
-                                const auto kernel = k_advance<decltype(mode)::value, decltype(fast)::value, false, true>;
-                                return launch_blocks("k_advance", kernel, persistent_blocks(kernel, n), 0, view, n,
-                                    pos, index, g, stats, queue);
-                        }
-                        const auto kernel = k_advance<decltype(mode)::value, decltype(fast)::value>;
-                        return launch_blocks("k_advance", kernel, persistent_blocks(kernel, n), 0, view, n, pos,
-                            index, io, stats, queue);
-                });
-        });
-}
-
 /* One generation of a paged traverse: as tamd_k_step_dir with TURTLE_AMD_STEP_RESUME, the
  * finished rays (index[r][0] = -1) left out; stats add up over the generations */
 extern "C" int tamd_k_step_live(struct tamd_view view, long n, double * pos, const double * dir,
@@ -4489,19 +2845,10 @@ extern "C" int tamd_k_step_live(struct tamd_view view, long n, double * pos, con
             TURTLE_AMD_STEP_RESUME | TAMD_STEP_LIVE, cross, pg, stats, no_walk);
 }
 
-extern "C" int tamd_k_traverse_gen(long n, int first, const double * alt, const double * step,
-    int * live_index, int * medium, int * index, double * length, int * n_steps, int * n_cross,
-    double ceiling, int max_steps, unsigned long long * counters)
+extern "C" int tamd_k_project(struct tamd_proj proj, int inverse, long n, const double * a,
+    const double * b, double * c, double * d)
 {
-        return launch_items("k_traverse_gen", k_traverse_gen, n, 0, n, first, alt, step, live_index, medium,
-            index, length, n_steps, n_cross, ceiling, max_steps, counters);
-}
-
-extern "C" int tamd_k_crossings_gen(long n, const double * pos, const double * step, const int * live_index,
-    const int * medium, const int * n_cross, double * total, struct tamd_crossings rec)
-{
-        return launch_items("k_crossings_gen", k_crossings_gen, n, 0, n, pos, step, live_index, medium, n_cross,
-            total, rec);
+        return launch_items("k_project", k_project, n, 0, proj, inverse, n, a, b, c, d);
 }
 
 extern "C" int tamd_k_philox(long n, unsigned long long seed, unsigned long long stream,
@@ -4559,51 +2906,4 @@ extern "C" int tamd_k_hand_over_order(long n, const int * ids, const unsigned ch
                 return 1;
         }
         return launch_order(n, ids, keys, n_front, n_back, words, out);
-}
-
-extern "C" int tamd_k_resample(struct tamd_view view, const struct tamd_grid * grids, int from_map,
-    double z0, double dz, int is_signed, int flags, long n_blocks, uint16_t * out,
-    struct tamd_paging pg, unsigned long long * counters)
-{
-        if (tamd_dev_init()) return 1;
-        if (n_blocks <= 0) return 0;
-        /* the target's projection: a host field, read back from its table */
-        struct tamd_grid target;
-        if (tamd_dev_d2h(&target, grids, sizeof(target))) return 1;
-        const unsigned blocks = grid_for(n_blocks * 64, 256);
-        return with_constant<RS_MAP, RS_STACK>(from_map ? RS_MAP : RS_STACK, [&](auto source) {
-                return with_constant<TAMD_PROJ_LAMBERT, TAMD_PROJ_UTM, TAMD_PROJ_NONE>(target.proj.type, [&](auto type) {
-                        return launch_blocks("k_resample", k_resample<decltype(source)::value, decltype(type)::value>,
-                            blocks, 0, view, grids, z0, dz, is_signed, flags, n_blocks, out, pg, counters);
-                });
-        });
-}
-
-extern "C" int tamd_k_unblock(const uint16_t * blocked, int nx, int ny, int nbx, uint16_t * rows)
-{
-        return launch_items("k_unblock", k_unblock, (long)nx * ny, 0, blocked, nx, ny, nbx, rows);
-}
-
-extern "C" int tamd_k_fill_encode(const double * elevation, long ld, int nx, int ny, double z0, double dz,
-    int is_signed, int flags, uint16_t * codes, unsigned long long * counters)
-{
-        const long n = (long)nx * ny;
-        return launch_items("k_fill_encode", k_fill_encode, n, 0, elevation, ld, nx, n, z0, dz, is_signed, flags,
-            codes, counters);
-}
-
-extern "C" int tamd_k_fill_store(uint16_t * nodes, int nbx, int ix0, int iy0, int nx, int ny, int blank,
-    const uint16_t * codes)
-{
-        const int nwx = ((ix0 + nx - 1) >> 3) - (ix0 >> 3) + 1, nwy = ((iy0 + ny - 1) >> 3) - (iy0 >> 3) + 1;
-        const long n_blocks = (long)nwx * nwy;
-        return launch_items("k_fill_store", k_fill_store, n_blocks * 64, 0, nodes, nbx, ix0, iy0, nx, ny, nwx,
-            n_blocks, blank, codes);
-}
-
-extern "C" int tamd_k_nodes(const uint16_t * nodes, int nbx, int ix0, int iy0, int nx, int ny, double z0,
-    double dz, int is_signed, double * elevation, long ld)
-{
-        const long n = (long)nx * ny;
-        return launch_items("k_nodes", k_nodes, n, 0, nodes, nbx, ix0, iy0, nx, n, z0, dz, is_signed, elevation, ld);
 }

@@ -1,7 +1,7 @@
 /*
- * device_ctx.h -- what the two halves of the device layer share (C++ only, not installed): the
- * calling thread's context, which runtime.hip owns and the launch layer of device.hip reads, and
- * the error convention of both.
+ * device_ctx.h -- what runtime.hip and the units of kernels share (C++ only, not installed): the
+ * calling thread's context, which runtime.hip owns and the launchers read (device_launch.h), and
+ * the error convention of all.
  */
 #ifndef TAMD_DEVICE_CTX_H
 #define TAMD_DEVICE_CTX_H

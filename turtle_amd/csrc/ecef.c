@@ -1,6 +1,6 @@
 /*
  * ecef.c -- host entry points of the WGS84 transforms [ref src/turtle/
- * ecef.c:41-207].  The arithmetic is in device.hip; the scalar calls launch
+ * ecef.c:41-207].  The arithmetic is in points.hip; the scalar calls launch
  * it with n = 1.  They return void, as in the reference, so a device failure
  * can only be reported through the error handler (which by default exits).
  */

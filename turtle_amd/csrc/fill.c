@@ -3,7 +3,7 @@
  * or read into, rows of doubles in one call -- the loops of turtle_map_fill and
  * turtle_map_node over the window.
  *
- * A fill runs in two kernels (device.hip).  k_fill_encode turns the elevations into codes in
+ * A fill runs in two kernels (maps.hip).  k_fill_encode turns the elevations into codes in
  * a buffer of the call's own and counts the elements that turtle_map_fill would refuse; this
  * file reads the counters and then either raises, with the map exactly as it was, or commits:
  * k_fill_store puts the codes into the map's HBM copy in place, block by touched block, and

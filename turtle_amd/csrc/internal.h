@@ -6,8 +6,8 @@
  *   host (C99: error.c map.c hgt.c stack.c client.c stepper.c ecef.c batch.c)
  *        owns the opaque handles of the public API, file ingest, the error
  *        convention, and flattening a stepper into the POD tables below;
- *   device (runtime.hip: HBM and the stream; device.hip: every kernel and its
- *        launch).  All arithmetic of the path happens there.
+ *   device (runtime.hip: HBM and the stream; device.hip, points.hip, maps.hip,
+ *        sight.hip, rays.hip: the kernels, a family each, and their launches).  All arithmetic of the path happens there.
  */
 #ifndef TURTLE_AMD_INTERNAL_H
 #define TURTLE_AMD_INTERNAL_H
@@ -24,7 +24,7 @@ extern "C" {
 
 
 /* ------------------------------------------------------------------------ */
-/* Device layer (runtime.hip, device.hip).  Each returns 0 on success or a   */
+/* Device layer (runtime.hip, the units of kernels).  Each returns 0 or a    */
 /* non-zero value after recording a message readable with tamd_dev_error(). */
 /* ------------------------------------------------------------------------ */
 
@@ -46,7 +46,7 @@ int tamd_dev_stream_set(void * stream);
 int tamd_dev_sync(void);
 void tamd_dev_math_set(int strict); /* 1: reference-order arithmetic in k_trace */
 int tamd_dev_math_get(void);
-void tamd_dev_in_flight_set(int batches); /* the batches the thread keeps in flight (a hint: device.hip, trace_blocks_per_cu) */
+void tamd_dev_in_flight_set(int batches); /* the batches the thread keeps in flight (a hint: device_launch.h, trace_blocks_per_cu) */
 int tamd_dev_in_flight_get(void);
 
 int tamd_dev_malloc(void ** ptr, size_t bytes);

@@ -1,7 +1,7 @@
 /*
  * map.c -- a single DEM grid: host handle, HBM residency, scalar and batch
  * elevation [ref src/turtle/map.c:54-421].  The bilinear arithmetic itself is
- * in device.hip (d_grid_elevation); nothing here interpolates.
+ * in points.hip (k_elevation: d_grid_elevation); nothing here interpolates.
  */
 #include "host.h"
 

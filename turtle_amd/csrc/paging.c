@@ -6,7 +6,7 @@
  * the least recently used one when the stack is full.  A batch on the GPU
  * cannot stop at a query, so the same policy runs in ROUNDS: the kernels list
  * the items (rays, points) that met a tile that is not resident, with a bitmap
- * of the tiles they want (device.hip, "Paging"); the host brings those tiles
+ * of the tiles they want (device_common.h, "Paging"); the host brings those tiles
  * into HBM -- dropping the least recently wanted ones beyond the budget --
  * and runs the list again, until it is empty.  An item is only ever computed
  * against tiles that are resident, so the results are those of a stack with

@@ -2,7 +2,7 @@
  * projection.c -- map projections: the handle, the name parser and the host
  * entry points [ref src/turtle/projection.c:53-230, projection.h:29-46].  The
  * formulas (Lambert conformal conic I-IV/IIe/93, UTM by the Krueger series)
- * are evaluated on the device (d_project / d_unproject in device.hip).
+ * are evaluated on the device (k_project in device.hip: d_project / d_unproject).
  */
 #include "host.h"
 

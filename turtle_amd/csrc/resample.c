@@ -3,7 +3,7 @@
  * another map in one call, the loop of the reference's examples/example-projection.c
  * (turtle_map_node, turtle_projection_unproject, turtle_stack_elevation, turtle_map_fill).
  *
- * The kernel (k_resample, device.hip) writes a whole new HBM copy of the map.  This file
+ * The kernel (k_resample, maps.hip) writes a whole new HBM copy of the map.  This file
  * checks the arguments, runs the rounds of a paged stack (paging.c; the items are the
  * map's 8 x 8 blocks), and then commits the copy -- it becomes this device's copy, the
  * host rows are read back from it, the other devices' copies go stale -- or drops it,

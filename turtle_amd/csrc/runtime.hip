@@ -1,7 +1,8 @@
 /*
  * runtime.hip -- the calling thread's share of the device: which gfx950 it works on, its stream,
  * HBM and pinned memory, the scratch arena and the grow-only blocks (internal.h: tamd_dev_*,
- * tamd_scratch_*).  No kernel is named here: they, and what launches them, are in device.hip.
+ * tamd_scratch_*).  No kernel is named here: they, and what launches them, are in the
+ * units of kernels (device.hip and the files beside it).
  */
 #include <sys/syscall.h>
 #include <unistd.h>

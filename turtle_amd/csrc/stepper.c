@@ -6,7 +6,7 @@
  * sources and walks them per sample on the CPU.  Here the same description is
  * kept in small host arrays and FLATTENED into POD tables in HBM
  * (internal.h); every sample, step and trace is then computed by the kernels
- * of device.hip.  Scalar entry points are the batch ones with n = 1.
+ * of device.hip, rays.hip and sight.hip.  Scalar entry points are the batch ones with n = 1.
  */
 #include "host.h"
 #include "trace_room.h"
